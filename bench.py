@@ -13,7 +13,12 @@ reference's signature flow). A *step* is a fixed batch of STEP_IOS
 random 4 KiB reads per GPU measured in-daemon on persistent queues;
 rank 0 prints one JSON line with the whole-job aggregate (weak scaling).
 
+A plain run sets up, warms up, times K steps and prints the result
+line; that is everything the benchmark measures, so --full (reserved
+for secondary measurements) currently adds nothing.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 """
 
 import argparse
@@ -26,7 +31,10 @@ import time
 
 # Persistent service kernels need one real HW queue each (ROCm default
 # is 4; beyond that MES time-slices them). Must precede HIP init.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+# Assigned, not defaulted: hosts that export the runtime's own default
+# of 4 would otherwise time-slice the 14 service kernels (measured
+# 30k IOPS instead of 12M). HIPSTORE_HW_QUEUES overrides.
+os.environ["GPU_MAX_HW_QUEUES"] = os.environ.get("HIPSTORE_HW_QUEUES", "24")
 
 
 def _set_affinity_base(num_queues: int) -> None:
@@ -54,6 +62,100 @@ REPO_ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO_ROOT)
 
 STEP_IOS = 131072  # 4 KiB reads per GPU per step (512 MiB moved)
+
+# --dump-outputs: the timed path hands its caller counters only (the
+# read payloads land in daemon-side pinned buffers), so the dump holds
+# the last timed step's I/O count plus a fixed, seeded sample of the
+# volume: DUMP_SAMPLE_IOS units are written with a seeded pattern before
+# warm-up and read back through the bdev's vhost attachment after the
+# timed steps — the bytes the engine serves from HBM for those offsets.
+DUMP_SAMPLE_IOS = 256
+DUMP_SEED = 0x0D0D
+DUMP_MAX_IO = 512 << 10  # one I/O must fit the sample master's buffers
+
+
+class SampleIO:
+    """Seeded write-then-readback of a sample of the benchmark volume
+    through a short-lived vhost-user master (never concurrent with the
+    timed region's own session)."""
+
+    def __init__(self, vhost_sock, personality, bdev_info, io_size):
+        import random
+
+        import numpy as np
+
+        if io_size > DUMP_MAX_IO:
+            raise SystemExit(f"--dump-outputs supports --io-size up to "
+                             f"{DUMP_MAX_IO}")
+        self.vhost_sock = vhost_sock
+        self.personality = personality
+        self.block_size = bdev_info.block_size
+        self.io_size = io_size
+        units = bdev_info.size_bytes // io_size
+        # float32 on disk is 4 bytes per sampled byte: stay under 48 MiB
+        count = min(DUMP_SAMPLE_IOS, units, (48 << 20) // (4 * io_size))
+        self.units = sorted(random.Random(DUMP_SEED).sample(
+            range(units), count))
+        self.pattern = np.random.default_rng(DUMP_SEED).integers(
+            0, 256, size=(count, io_size), dtype=np.uint8)
+
+    def _master(self):
+        from oim_amd.bench.vhost_client import VhostUserMaster
+        master = VhostUserMaster(
+            self.vhost_sock, queue=0 if self.personality == "blk" else 2)
+        master.negotiate()
+        return master
+
+    def seed(self):
+        master = self._master()
+        try:
+            for unit, row in zip(self.units, self.pattern):
+                offset = unit * self.io_size
+                if self.personality == "blk":
+                    status, _ = master.blk_write(offset // 512, row.tobytes())
+                else:
+                    status = master.write16(
+                        0, offset // self.block_size, row.tobytes(),
+                        self.block_size).status
+                if status != 0:
+                    raise RuntimeError(f"sample write failed at {offset}")
+        finally:
+            master.close()
+
+    def read_back(self):
+        import numpy as np
+
+        rows = []
+        master = self._master()
+        try:
+            for unit in self.units:
+                offset = unit * self.io_size
+                if self.personality == "blk":
+                    status, data = master.blk_read(offset // 512,
+                                                   self.io_size)
+                else:
+                    result = master.read16(
+                        0, offset // self.block_size,
+                        self.io_size // self.block_size, self.block_size)
+                    status, data = result.status, result.data
+                if status != 0:
+                    raise RuntimeError(f"sample read failed at {offset}")
+                rows.append(np.frombuffer(data, dtype=np.uint8))
+        finally:
+            master.close()
+        return np.stack(rows)
+
+
+def write_dump(directory, sample, last_step):
+    """DIR/io_count.npy (float64) and DIR/readback.npy (float32, one row
+    per sampled I/O unit; 4 MiB at the default --io-size)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "io_count.npy"),
+            np.array([last_step["io_count"]], dtype=np.float64))
+    np.save(os.path.join(directory, "readback.npy"),
+            sample.read_back().astype(np.float32))
 
 
 def start_stack(rank, local_rank, use_gpu, args, tmp):
@@ -188,7 +290,19 @@ def main() -> int:
                         help="vhost frontend driver: the C++ master "
                              "(measures the daemon's ceiling) or the "
                              "Python conformance master")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps write DIR/io_count.npy "
+                             "(I/Os the last step completed) and "
+                             "DIR/readback.npy (seeded sample of the volume "
+                             "read back through its vhost attachment), "
+                             "both from rank 0")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the benchmark's secondary "
+                             "measurements; it has none today, so this "
+                             "is the plain run")
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -212,12 +326,20 @@ def main() -> int:
     if not use_gpu:
         args.bdev_gb = min(args.bdev_gb, 1.0)
 
-    with tempfile.TemporaryDirectory(prefix="oim-bench-") as tmp:
+    # Every socket of the stack lives in this directory and AF_UNIX
+    # paths stop at 107 chars: keep clear of a deep system temp dir.
+    tmp_root = tempfile.gettempdir()
+    if len(tmp_root) > 64:
+        tmp_root = "/tmp"
+    with tempfile.TemporaryDirectory(prefix="oim-bench-",
+                                     dir=tmp_root) as tmp:
         client, volume, daemon_sock, cleanup = start_stack(
             rank, local_rank, use_gpu, args, tmp)
         try:
             session = None
             attachment = None
+            vhost_session = None
+            sample = None
             if args.frontend == "vhost":
                 # Timed region crosses the virtqueue: an in-process
                 # vhost-user master (synthetic guest) drives request
@@ -236,6 +358,10 @@ def main() -> int:
                 bdev_info = hipstore_mod.get_bdevs(client, volume)[0]
                 vhost_sock = os.path.join(os.path.dirname(daemon_sock),
                                           ctrlr)
+                if args.dump_outputs and rank == 0:
+                    sample = SampleIO(vhost_sock, args.personality,
+                                      bdev_info, args.io_size)
+                    sample.seed()
 
                 if args.vhost_master == "native":
                     # C++ master, ONE standing session: the handshake
@@ -289,6 +415,15 @@ def main() -> int:
                         return {"io_count": count, "iops": count / dt,
                                 "lat_p99_us": p99}
             else:
+                if args.dump_outputs and rank == 0:
+                    from oim_amd import hipstore as hipstore_mod
+
+                    # MapVolume attached the bdev to vhost.0, target 0.
+                    sample = SampleIO(
+                        os.path.join(os.path.dirname(daemon_sock), "vhost.0"),
+                        "scsi", hipstore_mod.get_bdevs(client, volume)[0],
+                        args.io_size)
+                    sample.seed()
                 session = client.invoke("perf_session_start", {
                     "bdev_name": volume,
                     "workload": args.workload,
@@ -330,6 +465,11 @@ def main() -> int:
                 client.invoke("perf_session_stop", {"session_id": session})
             if attachment is not None:
                 attachment.close()
+            if sample is not None:
+                # Drop the standing native session (run_step shares this
+                # variable) so the controller accepts the sample master.
+                vhost_session = None
+                write_dump(args.dump_outputs, sample, r)
         finally:
             cleanup()
 

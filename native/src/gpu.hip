@@ -2160,6 +2160,11 @@ PerfResult run_bdevperf(Bdev* bdev, const std::string& workload,
         uint8_t* buf = static_cast<uint8_t*>(
             alloc_pinned(static_cast<size_t>(io_size) * queue_depth));
         if (dbg) fprintf(stderr, "[hipstore-dbg] q%d pinned-buf\n", q);
+        // Writes carry a defined pattern, not whatever the allocator
+        // handed back (zero pages or stale heap contents).
+        if (do_write) {
+          memset(buf, 0x5A, static_cast<size_t>(io_size) * queue_depth);
+        }
         std::mt19937_64 rng(0x9E3779B97F4A7C15ULL ^ (q * 0x8DA6B343));
         QueueStats& st = stats[q];
         std::vector<clock::time_point> submit_ts(queue_depth);

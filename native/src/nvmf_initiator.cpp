@@ -12,6 +12,7 @@
 #include <netinet/in.h>
 #include <netinet/tcp.h>
 #include <poll.h>
+#include <sched.h>
 #include <sys/socket.h>
 #include <unistd.h>
 
@@ -237,6 +238,7 @@ class NvmfChannel : public IoChannel {
   std::map<uint16_t, InflightIo> inflight;
   std::vector<std::pair<IoCompletion, int>> immediate;  // failed at submit
   std::string rxbuf;
+  uint32_t idle_polls = 0;
 
   ~NvmfChannel() override = default;
 
@@ -367,6 +369,13 @@ class NvmfBdev : public Bdev {
       start += ch_hdr.plen;
     }
     channel->rxbuf.erase(0, start);
+    // Callers spin on poll(); every 32nd empty one offers the core so a
+    // target thread scheduled onto it is not held off until the tick.
+    if (completed != 0 || start != 0 || channel->inflight.empty()) {
+      channel->idle_polls = 0;
+    } else if ((++channel->idle_polls & 31) == 0) {
+      sched_yield();
+    }
     return completed;
   }
 

@@ -518,6 +518,7 @@ class TargetImpl : public NvmfTcpTarget,
       fcntl(fd, F_SETFL, flags | O_NONBLOCK);
     }
     std::string rx;
+    uint32_t idle_spins = 0;
     while (running_.load() && !dead) {
       char tmp[65536];
       while (true) {
@@ -551,7 +552,15 @@ class TargetImpl : public NvmfTcpTarget,
       for (auto& [bdev, channel] : channels) {
         completed += bdev->poll(channel.get());
       }
-      if (completed == 0) __builtin_ia32_pause();
+      if (completed == 0 && start == 0) {
+        __builtin_ia32_pause();
+        // Every 32nd idle spin, offer the core: when the scheduler has
+        // placed the peer's polling thread on this core, a pure spinner
+        // holds it until the next tick and each I/O costs milliseconds.
+        if ((++idle_spins & 31) == 0) sched_yield();
+      } else {
+        idle_spins = 0;
+      }
     }
     // Drain in-flight completions so pool buffers are not freed under
     // a pending I/O.

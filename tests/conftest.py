@@ -7,7 +7,11 @@ Markers:
 
 import faulthandler
 import os
+import pathlib
+import shutil
+import stat
 import sys
+import tempfile
 
 import pytest
 
@@ -49,6 +53,63 @@ def pytest_runtest_protocol(item, nextitem):
         yield
     finally:
         faulthandler.cancel_dump_traceback_later()
+
+
+def _short_tmp_root():
+    """The system temp dir when its path is short, else /tmp."""
+    root = tempfile.gettempdir()
+    return root if len(root) <= 16 else "/tmp"
+
+
+@pytest.fixture
+def tmp_path():
+    """A short per-test directory, replacing pytest's own ``tmp_path``.
+
+    Nearly every test binds unix sockets (hipstored, vhost controllers,
+    gRPC endpoints) below this directory, and AF_UNIX paths are limited
+    to 107 chars. pytest's default
+    ``<tmpdir>/pytest-of-<user>/pytest-N/<test name>0`` overflows that
+    under a long temp dir, user name or test name; the daemon then
+    refuses to start.
+    """
+    path = tempfile.mkdtemp(prefix="oim-", dir=_short_tmp_root())
+    yield pathlib.Path(path)
+    shutil.rmtree(path, ignore_errors=True)
+
+
+@pytest.fixture(scope="session")
+def _mknod_permitted():
+    """Whether this process may create block device nodes (CAP_MKNOD)."""
+    probe_dir = tempfile.mkdtemp(prefix="oim-", dir=_short_tmp_root())
+    try:
+        os.mknod(os.path.join(probe_dir, "probe"), stat.S_IFBLK | 0o600,
+                 os.makedev(1, 3))
+        return True
+    except PermissionError:
+        return False
+    finally:
+        shutil.rmtree(probe_dir, ignore_errors=True)
+
+
+@pytest.fixture
+def mknod_calls(_mknod_permitted, monkeypatch):
+    """Let the CSI remote backend "create" device nodes unprivileged.
+
+    With CAP_MKNOD the real ``os.mknod`` runs and the list stays empty.
+    Without it, ``os.mknod`` is replaced for the test by a recorder that
+    appends ``(path, mode, device)`` and leaves a plain file at ``path``,
+    so tests check the arguments at the syscall boundary instead of the
+    node's ``st_rdev``.
+    """
+    calls = []
+    if not _mknod_permitted:
+        def fake_mknod(path, mode=0o600, device=0):
+            calls.append((path, mode, device))
+            with open(path, "xb"):
+                pass
+
+        monkeypatch.setattr(os, "mknod", fake_mknod)
+    return calls
 
 
 @pytest.fixture

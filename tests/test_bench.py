@@ -42,7 +42,10 @@ class TestBenchContract:
         assert result["scaling"] == "weak"
 
     def test_two_rank_gloo(self):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29517")
+        # Hide any GPU: this is the CPU/gloo contract run, and two ranks
+        # must not compete for (or index past) a single card.
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29517",
+                   HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
         proc = subprocess.run(
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
              "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -59,6 +62,44 @@ class TestBenchContract:
         measured_ios = result["value"] * result["ms_per_step"] \
             * result["steps"] / 1000
         assert abs(measured_ios - expected_ios) / expected_ios < 0.01
+
+    @pytest.mark.parametrize("extra", [
+        [], ["--frontend", "vhost", "--queue-depth", "8",
+             "--vhost-numjobs", "2"]], ids=["daemon", "vhost"])
+    def test_dump_outputs(self, tmp_path, extra):
+        """--dump-outputs writes the last step's I/O count and the
+        seeded volume sample exactly as it was written."""
+        import numpy as np
+
+        dump_seed, dump_sample_ios = 0x0D0D, 256  # bench.py's constants
+        out = tmp_path / "dump"
+        proc = subprocess.run(
+            [sys.executable, BENCH, "--steps", "2", "--warmup", "0",
+             "--bdev-gb", "0.25", "--full", "--dump-outputs", str(out)]
+            + extra,
+            capture_output=True, text=True, timeout=600, cwd=REPO_ROOT)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        result = last_json_line(proc.stdout)
+        assert result["steps"] == 2 and result["ms_per_step"] > 0
+        assert sorted(p.name for p in out.iterdir()) == [
+            "io_count.npy", "readback.npy"]
+        io_count = np.load(out / "io_count.npy")
+        assert io_count.dtype == np.float64
+        # Each queue rounds its share of the step up, so a step completes
+        # at most one extra I/O per queue; both timed steps do the same
+        # work, which the result line's totals must reproduce.
+        step_ios = result["config"]["step_ios_per_gpu"]
+        assert io_count.shape == (1,)
+        assert step_ios <= io_count[0] < step_ios + \
+            result["config"]["num_queues"]
+        measured_ios = result["value"] * result["ms_per_step"] \
+            * result["steps"] / 1000
+        assert abs(measured_ios - 2 * io_count[0]) / measured_ios < 0.01
+        readback = np.load(out / "readback.npy")
+        assert readback.dtype == np.float32
+        expected = np.random.default_rng(dump_seed).integers(
+            0, 256, size=(dump_sample_ios, 4096), dtype=np.uint8)
+        assert np.array_equal(readback, expected.astype(np.float32))
 
     def test_vhost_frontend_single_process(self):
         proc = subprocess.run(

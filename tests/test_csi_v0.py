@@ -32,7 +32,7 @@ from test_csidriver import add_sysfs_device  # same fake-sysfs helper
 
 
 @pytest.fixture
-def control_plane03(hipstored, tmp_path):  # noqa: F811
+def control_plane03(hipstored, tmp_path, mknod_calls):  # noqa: F811
     """Full remote-mode stack serving the 0.3 personality with the
     ceph-csi emulation hook active (the deployment the twins exist
     for: deploy/kubernetes/ceph-csi oim-node.yaml --emulate=ceph-csi

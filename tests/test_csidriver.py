@@ -3,6 +3,7 @@ control plane (reference nodeserver_test.go, oim-driver_test.go).
 """
 
 import os
+import stat
 import threading
 import time
 
@@ -59,7 +60,7 @@ class TestFindDevice:
         # wrong PCI address: no match
         assert backend.find_device(parse_bdf_string("0000:00:16.0"), 3, 0) is None
 
-    def test_wait_sees_delayed_symlink(self, tmp_path):
+    def test_wait_sees_delayed_symlink(self, tmp_path, mknod_calls):
         """Device appears 0.5s after the wait starts
         (reference nodeserver_test.go delayed-symlink case)."""
         backend = self.make_backend(tmp_path)
@@ -76,8 +77,13 @@ class TestFindDevice:
         finally:
             thread.join()
         assert path.endswith("/sdb")
-        st = os.stat(path)
-        assert os.major(st.st_rdev) == 8 and os.minor(st.st_rdev) == 32
+        if mknod_calls:  # no CAP_MKNOD: the node was requested, not made
+            assert mknod_calls == [
+                (path, stat.S_IFBLK | 0o600, os.makedev(8, 32))]
+        else:
+            st = os.stat(path)
+            assert stat.S_ISBLK(st.st_mode)
+            assert os.major(st.st_rdev) == 8 and os.minor(st.st_rdev) == 32
 
     def test_wait_times_out(self, tmp_path):
         backend = self.make_backend(tmp_path)
@@ -159,7 +165,7 @@ class TestLocalBackendVolumes:
 
 
 @pytest.fixture
-def control_plane(hipstored, tmp_path):  # noqa: F811
+def control_plane(hipstored, tmp_path, mknod_calls):  # noqa: F811
     """registry + controller(hipstored) + CSI driver in remote mode with
     fake sysfs + FakeExec mounts (reference oim-driver_test.go:148-226)."""
     registry = Registry(db=MemRegistryDB())
