@@ -35,4 +35,9 @@ uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, size_t len2);
 void crc32c_hbm_blocks(Bdev* bdev, uint64_t offset, uint32_t block_size,
                        uint32_t count, uint32_t* out);
 
+// CRC32C of the whole range [offset, offset+length): per-4 KiB block
+// CRCs from crc32c_hbm_blocks folded left to right with
+// crc32c_combine. `length` must be a non-zero multiple of 4096.
+uint32_t crc32c_hbm_range(Bdev* bdev, uint64_t offset, uint64_t length);
+
 }  // namespace hipstore

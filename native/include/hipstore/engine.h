@@ -68,7 +68,9 @@ void free_pinned(void* ptr);
 // rebuild): same-device copies run the LDS-staged block kernel at HBM
 // rates; cross-device copies go over xGMI peer access. Returns
 // IoStatus; kIoInvalid when either bdev is not HBM-resident or ranges
-// are out of bounds/misaligned.
+// are out of bounds/misaligned (offsets and length are multiples of
+// 16: the kernel moves float4 elements) or overlap in device memory
+// (a grid-stride copy is neither memcpy nor memmove on overlap).
 int hbm_copy_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
                   uint64_t dst_offset, uint64_t length);
 
@@ -77,6 +79,58 @@ int hbm_copy_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
 int bdev_read_sync(Bdev* bdev, uint64_t offset, void* buf, uint64_t len);
 int bdev_write_sync(Bdev* bdev, uint64_t offset, const void* buf, uint64_t len);
 int bdev_fill_sync(Bdev* bdev, uint64_t offset, uint8_t value, uint64_t len);
+
+// Queued-I/O primitive for tests: holds ONE channel from get_channel()
+// for its lifetime (the way the daemon and the benchmark use channels)
+// and runs a list of requests with all of them in flight at once.
+// Works on any Bdev, so the same harness runs on the CPU malloc bdev.
+class IoQueue {
+ public:
+  struct Op {
+    IoOp op = IoOp::kRead;
+    uint64_t offset = 0;
+    uint64_t length = 0;   // writes: payload.size()
+    uint8_t fill = 0;
+    std::string payload;   // write data
+  };
+  struct Result {
+    int status = kIoFailed;  // IoStatus
+    bool has_data = false;   // successful read
+    std::string data;
+  };
+
+  explicit IoQueue(BdevPtr bdev);
+
+  // "batched" / "persistent" / "shared" for HBM channels (read from the
+  // channel's own kind tag), "cpu" for bdevs without a device base.
+  const char* kind() const;
+
+  // Submits every op in order before the first poll(), then polls
+  // until all completions fired. Requests go to the engine exactly as
+  // given (no chunking, no validation). One pinned arena per call
+  // carries write payloads in and read results out; it is kept and
+  // reused (grown when a call needs more) and only freed with the
+  // queue: hipHostFree waits for the device to go idle, so freeing
+  // after every call would stall ~1 s on a resident service kernel
+  // and force it through idle-exit + relaunch between any two calls.
+  // The wait is bounded by the sync-I/O timeout; on expiry this throws
+  // and leaks the arena (a descriptor may still point into it).
+  std::vector<Result> run(const std::vector<Op>& ops);
+
+  ~IoQueue();
+  IoQueue(const IoQueue&) = delete;
+  IoQueue& operator=(const IoQueue&) = delete;
+
+ private:
+  uint8_t* acquire_arena(uint64_t bytes);
+
+  BdevPtr bdev_;
+  std::shared_ptr<IoChannel> channel_;
+  uint8_t* arena_ = nullptr;
+  uint64_t arena_capacity_ = 0;
+  std::vector<void*> retired_;  // outgrown arenas, freed with the queue
+  bool busy_ = false;           // a run() left requests outstanding
+};
 
 // fio-shaped benchmark harness (SPDK bdevperf analog): `workload` is
 // randread / randwrite / randrw; runs num_queues submitter threads each

@@ -93,7 +93,9 @@ class MallocBdev : public Bdev {
   void submit(IoChannel* ch, IoRequest req) override {
     auto* channel = static_cast<MallocChannel*>(ch);
     int status = kIoOk;
-    if (!check_bounds(req)) {
+    // A flush carries no range (length 0), so bounds do not apply —
+    // same exemption as the HBM and composite bdevs.
+    if (req.op != IoOp::kFlush && !check_bounds(req)) {
       status = kIoInvalid;
     } else {
       account(req);
@@ -171,7 +173,9 @@ class FileBdev : public Bdev {
   void submit(IoChannel* ch, IoRequest req) override {
     auto* channel = static_cast<MallocChannel*>(ch);
     int status = kIoOk;
-    if (!check_bounds(req)) {
+    // A flush carries no range (length 0), so bounds do not apply —
+    // same exemption as the HBM and composite bdevs.
+    if (req.op != IoOp::kFlush && !check_bounds(req)) {
       status = kIoInvalid;
     } else {
       account(req);

@@ -1874,6 +1874,7 @@ void crc32c_hbm_blocks(Bdev* bdev, uint64_t offset, uint32_t block_size,
       offset + static_cast<uint64_t>(block_size) * count > bdev->size_bytes()) {
     throw std::runtime_error("crc32c: range out of bounds");
   }
+  if (count == 0) return;  // nothing to digest: no zero-sized launch
   void* base = bdev->device_base();
   if (base == nullptr) {
     crc32c_cpu_fallback(bdev, offset, block_size, count, out);
@@ -1912,6 +1913,23 @@ void crc32c_hbm_blocks(Bdev* bdev, uint64_t offset, uint32_t block_size,
   memcpy(out, ctx.out, count * 4);
 }
 
+uint32_t crc32c_hbm_range(Bdev* bdev, uint64_t offset, uint64_t length) {
+  constexpr uint32_t kDigestBlock = 4096;
+  if (length == 0 || length % kDigestBlock != 0 ||
+      length / kDigestBlock > UINT32_MAX) {
+    throw std::runtime_error(
+        "crc32c: range length must be a non-zero multiple of 4096");
+  }
+  const uint32_t count = static_cast<uint32_t>(length / kDigestBlock);
+  std::vector<uint32_t> crcs(count);
+  crc32c_hbm_blocks(bdev, offset, kDigestBlock, count, crcs.data());
+  uint32_t crc = crcs[0];
+  for (uint32_t i = 1; i < count; ++i) {
+    crc = crc32c_combine(crc, crcs[i], kDigestBlock);
+  }
+  return crc;
+}
+
 int hbm_copy_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
                   uint64_t dst_offset, uint64_t length) {
   uint8_t* src_base = static_cast<uint8_t*>(src->device_base());
@@ -1920,6 +1938,17 @@ int hbm_copy_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
   if (length == 0 || length % 16 != 0 ||
       src_offset + length > src->size_bytes() ||
       dst_offset + length > dst->size_bytes()) {
+    return kIoInvalid;
+  }
+  // float4 accesses: hipMalloc bases are 256-byte aligned, so the
+  // offsets decide the alignment of both pointers.
+  if (src_offset % 16 != 0 || dst_offset % 16 != 0) return kIoInvalid;
+  // Overlap (only possible within one backing store): the grid-stride
+  // kernel gives neither memcpy nor memmove semantics there.
+  const uint8_t* s0 = src_base + src_offset;
+  const uint8_t* d0 = dst_base + dst_offset;
+  if (src->gpu_device() == dst->gpu_device() && s0 < d0 + length &&
+      d0 < s0 + length) {
     return kIoInvalid;
   }
   const int src_dev = src->gpu_device();
@@ -2047,6 +2076,135 @@ int bdev_fill_sync(Bdev* bdev, uint64_t offset, uint8_t value, uint64_t len) {
   req.length = len;
   req.fill = value;
   return run_sync(bdev, std::move(req));
+}
+
+// ---------------------------------------------------------------------------
+// IoQueue: many requests in flight on one long-lived channel (tests)
+// ---------------------------------------------------------------------------
+
+IoQueue::IoQueue(BdevPtr bdev)
+    : bdev_(std::move(bdev)), channel_(bdev_->get_channel()) {}
+
+const char* IoQueue::kind() const {
+  // Only HbmBdev exposes a device base, and every channel it hands out
+  // derives from HbmChannelBase, whose tag is the single source of
+  // truth for the engine serving this queue.
+  if (bdev_->device_base() == nullptr) return "cpu";
+  switch (static_cast<HbmChannelBase*>(channel_.get())->kind) {
+    case HbmChannelBase::Kind::kBatched: return "batched";
+    case HbmChannelBase::Kind::kPersistent: return "persistent";
+    case HbmChannelBase::Kind::kShared: return "shared";
+  }
+  return "unknown";
+}
+
+std::vector<IoQueue::Result> IoQueue::run(const std::vector<Op>& ops) {
+  // Arena layout: one 64-byte-aligned region per read/write op (the
+  // batched kernel moves float4s, so every buffer is 16-aligned).
+  constexpr uint64_t kAlign = 64;
+  std::vector<uint64_t> region(ops.size(), 0);
+  uint64_t arena_bytes = kAlign;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    if (ops[i].op != IoOp::kRead && ops[i].op != IoOp::kWrite) continue;
+    region[i] = arena_bytes;
+    arena_bytes += (ops[i].length + kAlign - 1) / kAlign * kAlign + kAlign;
+  }
+  uint8_t* arena = acquire_arena(arena_bytes);
+  for (size_t i = 0; i < ops.size(); ++i) {
+    if (ops[i].op == IoOp::kWrite && ops[i].length > 0) {
+      memcpy(arena + region[i], ops[i].payload.data(), ops[i].length);
+    } else if (ops[i].op == IoOp::kRead) {
+      // The arena is reused: a read the engine completes without
+      // storing anything must not show an earlier call's bytes.
+      memset(arena + region[i], 0xDB, ops[i].length);
+    }
+  }
+
+  // Heap state shared with the callbacks: after a timeout this frame is
+  // gone while completions may still fire from a later poll().
+  struct RunState {
+    std::vector<int> status;
+    size_t remaining = 0;
+  };
+  auto state = std::make_shared<RunState>();
+  state->status.assign(ops.size(), kIoFailed);
+  state->remaining = ops.size();
+
+  // From the first submit on, any exception (a HIP error from the
+  // engine, the timeout below) leaves busy_ set, and the arena is then
+  // leaked on purpose: a descriptor already in a ring may still point
+  // into it (same rule as run_bdevperf's stall path).
+  busy_ = true;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    IoRequest req;
+    req.op = ops[i].op;
+    req.offset = ops[i].offset;
+    req.length = ops[i].length;
+    req.fill = ops[i].fill;
+    if (req.op == IoOp::kRead || req.op == IoOp::kWrite) {
+      req.buffer = arena + region[i];
+    }
+    req.on_complete = [state, i](int status) {
+      state->status[i] = status;
+      --state->remaining;
+    };
+    bdev_->submit(channel_.get(), std::move(req));
+  }
+  const auto deadline = std::chrono::steady_clock::now() +
+                        std::chrono::duration<double>(sync_io_timeout_s());
+  while (state->remaining > 0) {
+    bdev_->poll(channel_.get());
+    if (state->remaining > 0 &&
+        std::chrono::steady_clock::now() > deadline) {
+      dump_engine_stats("IoQueue timeout");
+      throw std::runtime_error(
+          "IoQueue: " + std::to_string(state->remaining) + " of " +
+          std::to_string(ops.size()) + " requests still outstanding after " +
+          std::to_string(sync_io_timeout_s()) + " s");
+    }
+  }
+
+  std::vector<Result> results(ops.size());
+  for (size_t i = 0; i < ops.size(); ++i) {
+    results[i].status = state->status[i];
+    if (ops[i].op == IoOp::kRead && state->status[i] == kIoOk) {
+      results[i].has_data = true;
+      results[i].data.assign(reinterpret_cast<const char*>(arena + region[i]),
+                             ops[i].length);
+    }
+  }
+  busy_ = false;
+  return results;
+}
+
+uint8_t* IoQueue::acquire_arena(uint64_t bytes) {
+  if (busy_) {
+    // The previous run() ended with requests outstanding: abandon its
+    // buffers instead of handing them to new requests or freeing them.
+    arena_ = nullptr;
+    arena_capacity_ = 0;
+    retired_.clear();
+    busy_ = false;
+  }
+  if (bytes > arena_capacity_) {
+    if (arena_ != nullptr) retired_.push_back(arena_);
+    arena_ = nullptr;
+    arena_capacity_ = 0;
+    void* p = alloc_pinned(bytes);
+    if (p == nullptr) throw std::runtime_error("IoQueue: arena allocation");
+    arena_ = static_cast<uint8_t*>(p);
+    arena_capacity_ = bytes;
+  }
+  return arena_;
+}
+
+IoQueue::~IoQueue() {
+  // Channel first (it drains its rings and, for the per-queue engine,
+  // stops its service kernel), then the buffers its descriptors named.
+  channel_.reset();
+  if (busy_) return;  // outstanding requests: leak, see run()
+  for (void* p : retired_) free_pinned(p);
+  free_pinned(arena_);
 }
 
 // ---------------------------------------------------------------------------

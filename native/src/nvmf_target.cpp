@@ -43,19 +43,17 @@ using namespace nvmf;
 // the bytes: measured crossover is around 1 MiB. Below that the
 // hardware-CRC host path is strictly faster (128 KiB digest path:
 // 0.57 -> ~5 GB/s).
+// Consequence: the read path only digests PDUs of at most
+// kMaxDataPerPdu (128 KiB) and always has a host copy, so the GPU
+// branch below is currently unreachable from NVMe-oF; every C2HData
+// digest comes from the host CRC. The shared ladder it would use is
+// crc32c_hbm_range, which has its own tests.
 uint32_t range_crc32c(Bdev* bdev, uint64_t offset, const void* host_copy,
                       uint32_t len) {
   if (bdev->device_base() != nullptr &&
       (host_copy == nullptr || len >= (1u << 20)) && len % 4096 == 0 &&
-      offset % 4096 == 0) {
-    const uint32_t blocks = len / 4096;
-    std::vector<uint32_t> crcs(blocks);
-    crc32c_hbm_blocks(bdev, offset, 4096, blocks, crcs.data());
-    uint32_t crc = crcs[0];
-    for (uint32_t i = 1; i < blocks; ++i) {
-      crc = crc32c_combine(crc, crcs[i], 4096);
-    }
-    return crc;
+      len != 0 && offset % 4096 == 0) {
+    return crc32c_hbm_range(bdev, offset, len);
   }
   return crc32c_sw(0, host_copy, len);
 }

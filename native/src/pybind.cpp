@@ -56,6 +56,59 @@ void bdev_fill_py(Bdev& bdev, uint64_t offset, int value, uint64_t length) {
   }
 }
 
+// ("read", offset, length) / ("write", offset, bytes) /
+// ("fill", offset, length, value) / ("flush",) -> IoQueue::Op. No
+// validation of the request itself: that is the engine's job.
+IoQueue::Op io_op_from_tuple(const py::tuple& t) {
+  if (t.empty()) throw std::invalid_argument("IoQueue: empty op tuple");
+  const std::string name = t[0].cast<std::string>();
+  IoQueue::Op op;
+  if (name == "read" && t.size() == 3) {
+    op.op = IoOp::kRead;
+    op.offset = t[1].cast<uint64_t>();
+    op.length = t[2].cast<uint64_t>();
+  } else if (name == "write" && t.size() == 3) {
+    op.op = IoOp::kWrite;
+    op.offset = t[1].cast<uint64_t>();
+    py::buffer_info info = t[2].cast<py::buffer>().request();
+    op.payload.assign(static_cast<const char*>(info.ptr),
+                      static_cast<size_t>(info.size) * info.itemsize);
+    op.length = op.payload.size();
+  } else if (name == "fill" && t.size() == 4) {
+    op.op = IoOp::kFill;
+    op.offset = t[1].cast<uint64_t>();
+    op.length = t[2].cast<uint64_t>();
+    op.fill = static_cast<uint8_t>(t[3].cast<int>());
+  } else if (name == "flush" && t.size() == 1) {
+    op.op = IoOp::kFlush;
+  } else {
+    throw std::invalid_argument("IoQueue: unknown op tuple '" + name + "'");
+  }
+  return op;
+}
+
+py::list io_queue_run_py(IoQueue& q, const py::list& ops_py) {
+  std::vector<IoQueue::Op> ops;
+  ops.reserve(ops_py.size());
+  for (py::handle item : ops_py) {
+    ops.push_back(io_op_from_tuple(item.cast<py::tuple>()));
+  }
+  std::vector<IoQueue::Result> results;
+  {
+    py::gil_scoped_release release;
+    results = q.run(ops);
+  }
+  py::list out;
+  for (const IoQueue::Result& r : results) {
+    if (r.has_data) {
+      out.append(py::make_tuple(r.status, py::bytes(r.data)));
+    } else {
+      out.append(py::make_tuple(r.status, py::none()));
+    }
+  }
+  return out;
+}
+
 py::dict perf_to_dict(const PerfResult& r) {
   py::dict d;
   d["seconds"] = r.seconds;
@@ -177,6 +230,13 @@ PYBIND11_MODULE(_hipstore, m) {
       py::arg("total_ios") = 100000, py::arg("block_size") = 512,
       py::arg("capacity_bytes") = 0);
 
+  py::class_<IoQueue>(m, "IoQueue",
+                      "Queued I/O on one long-lived channel (tests): run() "
+                      "submits every op before the first poll")
+      .def(py::init<BdevPtr>(), py::arg("bdev"))
+      .def_property_readonly("kind", &IoQueue::kind)
+      .def("run", &io_queue_run_py, py::arg("ops"));
+
   py::class_<PerfSession>(m, "PerfSession")
       .def(py::init<BdevPtr, std::string, uint32_t, uint32_t, int>(),
            py::arg("bdev"), py::arg("workload") = "randread",
@@ -270,4 +330,12 @@ PYBIND11_MODULE(_hipstore, m) {
   }, py::arg("bdev"), py::arg("offset"), py::arg("block"), py::arg("count"),
      "CRC32C of `count` consecutive `block`-byte blocks of an HBM bdev, "
      "computed on-GPU");
+
+  m.def("crc32c_gpu_range", [](BdevPtr bdev, uint64_t offset,
+                               uint64_t length) {
+    py::gil_scoped_release release;
+    return crc32c_hbm_range(bdev.get(), offset, length);
+  }, py::arg("bdev"), py::arg("offset"), py::arg("length"),
+     "CRC32C of one range: per-4 KiB block CRCs folded with "
+     "crc32c_combine (the digest ladder of the NVMe-oF and rados paths)");
 }

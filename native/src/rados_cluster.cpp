@@ -269,14 +269,7 @@ class RadosClusterImpl : public RadosCluster,
                      uint64_t len) {
     if (hbm_ && offset % 4096 == 0 && len % 4096 == 0 &&
         len >= (1ull << 20)) {
-      const uint32_t count = static_cast<uint32_t>(len / 4096);
-      std::vector<uint32_t> crcs(count);
-      crc32c_hbm_blocks(arena_.get(), offset, 4096, count, crcs.data());
-      uint32_t crc = crcs[0];
-      for (uint32_t i = 1; i < count; ++i) {
-        crc = crc32c_combine(crc, crcs[i], 4096);
-      }
-      return crc;
+      return crc32c_hbm_range(arena_.get(), offset, len);
     }
     std::vector<uint8_t> tmp(len);
     if (arena_read_any(channel, bounce, offset, tmp.data(), len) != kIoOk) {

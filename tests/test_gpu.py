@@ -89,8 +89,14 @@ class TestPersistentEngine:
         assert bdev.read(512, 512) == payload
 
     def test_idle_exit_and_relaunch(self, bdev):
-        """The service kernel self-exits when idle (~1s) and must
-        transparently relaunch on the next submission."""
+        """I/O keeps working across an idle period longer than the
+        service kernel's idle exit (~1 s).
+
+        This does NOT exercise relaunch: every bdev.write/read takes a
+        fresh channel, whose constructor launches a new service kernel
+        with a zero completed prefix. Relaunch from poll() on a live
+        channel (non-zero prefix) is covered by
+        test_engine_matrix.py::test_relaunch_on_live_channel."""
         import time
         bdev.write(0, b"\x11" * 512)
         time.sleep(2.5)  # beyond the idle timeout
@@ -139,6 +145,67 @@ class TestCrc32c:
 
     def test_known_answer(self):
         assert hs.crc32c(b"123456789") == 0xE3069283
+
+    @pytest.fixture(scope="class")
+    def digest_rig(self):
+        """8 MiB of random bytes on a 512-byte-block bdev + the same
+        bytes on the host (the reference input, never modified)."""
+        bdev = hs.create_hbm_bdev("crc-shapes", 512, 16384, device=0)
+        data = random.Random(17).randbytes(bdev.size_bytes)
+        bdev.write(0, data)
+        return bdev, data
+
+    @staticmethod
+    def _table_blocks(data, offset, block, count):
+        return [hs.crc32c_table(data[offset + i * block:
+                                     offset + (i + 1) * block])
+                for i in range(count)]
+
+    @pytest.mark.parametrize("block", [512, 4096])
+    def test_block_counts_and_offset(self, digest_rig, block):
+        """One lane per block: counts across the wave (64) and workgroup
+        (256) boundaries, several workgroups, and 1025 last so the
+        thread-local result buffer (1024 entries at first) grows after
+        smaller calls. Offset is block-aligned, not 4 KiB-aligned."""
+        bdev, data = digest_rig
+        offset = 3 * 512
+        for count in (1, 63, 64, 65, 255, 256, 257, 1025):
+            gpu = hs.crc32c_gpu_blocks(bdev, offset, block, count)
+            assert list(gpu) == self._table_blocks(data, offset, block,
+                                                   count), (block, count)
+        # offset 0 and a smaller call after the buffer grew
+        assert list(hs.crc32c_gpu_blocks(bdev, 0, block, 65)) == \
+            self._table_blocks(data, 0, block, 65)
+
+    def test_zero_count_is_empty(self, digest_rig):
+        bdev, _ = digest_rig
+        assert list(hs.crc32c_gpu_blocks(bdev, 512, 4096, 0)) == []
+
+    def test_rejects_bad_arguments(self, digest_rig):
+        bdev, _ = digest_rig
+        with pytest.raises(RuntimeError):
+            hs.crc32c_gpu_blocks(bdev, 0, 4098, 1)   # not a multiple of 4
+        with pytest.raises(RuntimeError):
+            hs.crc32c_gpu_blocks(bdev, bdev.size_bytes - 4096, 4096, 2)
+        with pytest.raises(RuntimeError):
+            hs.crc32c_gpu_blocks(bdev, 100, 512, 1)  # offset not on a block
+
+    @pytest.mark.parametrize("offset,length", [
+        (0, 4096), (0, 8192), (0, (1 << 20) + 4096),
+        (5 * 512, 4096), (5 * 512, (1 << 20) + 4096)])
+    def test_range_digest(self, digest_rig, offset, length):
+        """Per-4 KiB GPU CRCs folded by the combine ladder (the digest
+        of the NVMe-oF and rados large-extent paths) against the table
+        CRC of the same bytes: one block (no combine), two, and 257."""
+        bdev, data = digest_rig
+        assert hs.crc32c_gpu_range(bdev, offset, length) == \
+            hs.crc32c_table(data[offset:offset + length])
+
+    def test_range_digest_rejects_partial_blocks(self, digest_rig):
+        bdev, _ = digest_rig
+        for length in (0, 512, 4096 + 512):
+            with pytest.raises(RuntimeError):
+                hs.crc32c_gpu_range(bdev, 0, length)
 
 
 @needs_gpu
@@ -234,6 +301,69 @@ class TestHbmCopy:
         hs.hbm_copy(a, 4096, b, 0, 512)
         assert b.read(0, 4096)[:512] == blob[:512]
 
+    SENTINEL = 0xEE
+
+    @pytest.fixture(scope="class")
+    def copy_rig(self):
+        """Source bdev holding random bytes (the reference input) and a
+        destination bdev; both 512-byte blocks, 16 MiB."""
+        src = hs.create_hbm_bdev("cp-src", 512, 32768, device=0)
+        dst = hs.create_hbm_bdev("cp-dst", 512, 32768, device=0)
+        blob = random.Random(57).randbytes(src.size_bytes)
+        src.write(0, blob)
+        return src, dst, blob
+
+    @pytest.mark.parametrize("length", [16, 4080, 4096 + 16,
+                                        (8 << 20) + 48])
+    def test_range_copy_edges(self, copy_rig, length):
+        """k_copy_range at float4 counts that are no multiple of the
+        256-thread workgroup; (8 MiB + 48) / 16 = 2048*256 + 3 elements
+        makes the grid-stride loop run a second, ragged pass. Offsets
+        are 16-aligned but not block- or tile-aligned; the destination
+        is pre-filled so bytes on either side must stay untouched."""
+        src, dst, blob = copy_rig
+        src_off = 4096 + 48
+        dst_off = 8192 + 80
+        dst.fill(0, self.SENTINEL, dst.size_bytes)
+        hs.hbm_copy(src, src_off, dst, dst_off, length)
+        lo = (dst_off - 16) // 512 * 512
+        hi = -(-(dst_off + length + 16) // 512) * 512
+        region = dst.read(lo, hi - lo)
+        head = dst_off - lo
+        assert region[:head] == bytes([self.SENTINEL]) * head
+        assert region[head:head + length] == blob[src_off:src_off + length]
+        tail = len(region) - head - length
+        assert tail >= 16
+        assert region[head + length:] == bytes([self.SENTINEL]) * tail
+
+    def test_rejects_misaligned_offsets(self, copy_rig):
+        src, dst, _ = copy_rig
+        for src_off, dst_off in ((8, 0), (0, 8), (4100, 4096), (16, 4097)):
+            with pytest.raises(RuntimeError):
+                hs.hbm_copy(src, src_off, dst, dst_off, 4096)
+
+    def test_rejects_overlap_within_one_bdev(self, copy_rig):
+        src, _, blob = copy_rig
+        for src_off, dst_off, length in ((0, 16, 4096),       # forward
+                                         (4096, 4096 - 16, 4096),  # backward
+                                         (8192, 8192, 512),   # identical
+                                         (0, 4096 - 16, 4096)):  # last 16 B
+            with pytest.raises(RuntimeError):
+                hs.hbm_copy(src, src_off, src, dst_off, length)
+        # rejected before any launch: the source is unchanged
+        assert src.read(0, 16384) == blob[:16384]
+
+    def test_copy_within_one_bdev(self):
+        bdev = hs.create_hbm_bdev("cp-self", 512, 4096, device=0)
+        blob = random.Random(59).randbytes(8192)
+        bdev.write(0, blob)
+        # adjacent, not overlapping: [16, 4112) -> [4112, 8208)
+        hs.hbm_copy(bdev, 16, bdev, 4096 + 16, 4096)
+        expect = bytearray(blob + b"\0" * 512)
+        expect[4112:8208] = blob[16:4112]
+        assert len(expect) == 8704
+        assert bdev.read(0, 8704) == bytes(expect)
+
     def test_rejects_cpu_bdev(self):
         a = hs.create_hbm_bdev("cp-c", 4096, 1024, device=0)
         c = hs.create_malloc_bdev("cp-d", 4096, 1024)
@@ -255,10 +385,16 @@ class TestHbmCopy:
 @needs_gpu
 class TestNvmfGpu:
     def test_hbm_namespace_gpu_digest_roundtrip(self):
-        """NVMe/TCP loopback with an HBM-resident namespace: C2HData
-        digests for aligned >=16 KiB reads are produced by the GPU
-        CRC32C kernel + host combine; the initiator verifies them in
-        software, so a mismatch anywhere fails the read."""
+        """NVMe/TCP loopback with an HBM-resident namespace; the
+        initiator verifies every C2HData digest in software, so a
+        mismatch anywhere fails the read.
+
+        The digests here come from the HOST CRC, not the GPU kernel:
+        the target digests PDUs of at most 128 KiB and takes the GPU
+        branch only from 1 MiB up when it holds a host copy, so that
+        branch cannot be reached from the NVMe-oF read path. The GPU
+        per-4 KiB CRC + combine ladder is tested directly by
+        TestCrc32c::test_range_digest."""
         backing = hs.create_hbm_bdev("nvmf-hbm", 4096, 16384, device=0)
         target = hs.start_nvmf_tcp_target(
             "", 0, "nqn.2026-01.com.amd:gpu-ns", True)
@@ -270,7 +406,7 @@ class TestNvmfGpu:
             rng = random.Random(31)
             data = bytes(rng.getrandbits(8) for _ in range(128 * 1024))
             bdev.write(0, data)
-            # 128 KiB aligned read -> GPU-digested C2HData
+            # 128 KiB aligned read -> one digested C2HData PDU
             assert bdev.read(0, len(data)) == data
             assert backing.read(0, len(data)) == data
             r = hs.run_bdevperf(bdev, "randread", 65536, 8, 2, 0.5)
@@ -432,6 +568,29 @@ class TestHbmResize:
         assert bdev.read(65535 * 512, 512) == tail
         # grown region arrived zeroed
         assert bdev.read(4096, 512) == b"\0" * 512
+
+    def test_grow_from_three_blocks(self):
+        """Kept prefix of 1536 bytes: 96 float4s, less than one
+        workgroup and no multiple of a tile."""
+        bdev = hs.create_hbm_bdev("resize-1", 512, 3, device=0)
+        data = random.Random(61).randbytes(1536)
+        bdev.write(0, data)
+        assert bdev.resize(64) == 0
+        assert bdev.num_blocks == 64
+        assert bdev.read(0, 64 * 512) == data + b"\0" * (61 * 512)
+
+    def test_shrink_then_grow_shows_zeros(self):
+        bdev = hs.create_hbm_bdev("resize-2", 512, 24, device=0)
+        data = random.Random(62).randbytes(24 * 512)
+        bdev.write(0, data)
+        assert bdev.resize(5) == 0            # shrink keeps the prefix
+        assert bdev.num_blocks == 5
+        assert bdev.read(0, 5 * 512) == data[:5 * 512]
+        with pytest.raises(RuntimeError):
+            bdev.read(5 * 512, 512)           # cut off
+        assert bdev.resize(24) == 0           # grow again
+        # the old tail is gone: zeros, not blocks 5..23 of `data`
+        assert bdev.read(0, 24 * 512) == data[:5 * 512] + b"\0" * (19 * 512)
 
 
 @pytest.mark.gpu

@@ -509,3 +509,152 @@ class TestTypedWrappers:
              "-C", "-c", str(garbage)],
             capture_output=True, text=True, timeout=30)
         assert proc.returncode == 1
+
+
+class TestIoModel:
+    """The byte model and op generator themselves, against
+    hand-written expectations."""
+
+    def test_model_applies_ops(self):
+        import io_model
+
+        model = io_model.ByteModel(8192)
+        expected = model.apply([
+            ("write", 512, b"\x11" * 1024),
+            ("fill", 4096, 1536, 0x1AB),     # value is taken modulo 256
+            ("read", 0, 512),
+            ("flush",),
+        ])
+        assert expected == [(0, None), (0, None), (0, b"\0" * 512), (0, None)]
+        assert bytes(model.data) == (b"\0" * 512 + b"\x11" * 1024
+                                     + b"\0" * 2560 + b"\xab" * 1536
+                                     + b"\0" * 2560)
+        # A later run sees the earlier one; reads straddle op edges.
+        expected = model.apply([("read", 1024, 1024), ("read", 5120, 1024)])
+        assert expected == [(0, b"\x11" * 512 + b"\0" * 512),
+                            (0, b"\xab" * 512 + b"\0" * 512)]
+
+    def test_model_rejects_what_the_engines_reject(self):
+        import io_model
+
+        model = io_model.ByteModel(8192)
+        before = bytes(model.data)
+        expected = model.apply([
+            ("read", 8192, 512),             # starts at the end
+            ("read", 7680, 1024),            # crosses the end
+            ("write", 0, b"x" * 100),        # not a block multiple
+            ("write", 512, b""),             # zero length
+            ("fill", 100, 512, 1),           # unaligned offset
+            ("flush",),
+        ])
+        assert [s for s, _ in expected] == [-22, -22, -22, -22, -22, 0]
+        assert bytes(model.data) == before
+
+    def test_model_refuses_overlap_inside_a_run(self):
+        import io_model
+
+        model = io_model.ByteModel(8192)
+        with pytest.raises(ValueError):
+            model.apply([("write", 0, b"a" * 1024), ("read", 512, 512)])
+        # Touching ranges are fine; so is the same range in the NEXT run.
+        model.apply([("write", 0, b"a" * 1024), ("read", 1024, 512)])
+        model.apply([("read", 512, 512)])
+
+    def test_check_names_the_first_wrong_byte(self):
+        import io_model
+
+        model = io_model.ByteModel(4096)
+        model.apply([("fill", 0, 1024, 7)])
+        good = b"\x07" * 1024
+        model.check([("read", 0, 1024)], [(0, good)])
+        with pytest.raises(AssertionError, match="byte 1023"):
+            model.check([("read", 0, 1024)], [(0, good[:-1] + b"\x08")])
+        with pytest.raises(AssertionError, match="status"):
+            model.check([("read", 0, 1024)], [(-5, None)])
+        with pytest.raises(AssertionError, match="1023 bytes"):
+            model.check([("read", 0, 1024)], [(0, good[:-1])])
+
+    def test_generator_runs_are_disjoint_and_seeded(self):
+        import io_model
+
+        size = 64 << 20
+        runs = []
+        for _ in range(2):
+            gen = io_model.OpGenerator(size, seed=99)
+            runs.append([gen.batch(33, kinds=("write", "fill", "read"))
+                         for _ in range(3)])
+        assert runs[0] == runs[1]                     # same seed, same ops
+        other = io_model.OpGenerator(size, seed=100).batch(33)
+        assert other != runs[0][0]
+        everything = [op for run in runs[0] for op in run]
+        io_model.assert_disjoint(everything)          # even across runs
+        io_model.assert_disjoint(
+            everything + io_model.guard_reads(everything))
+        lengths = {io_model.op_length(op) for op in everything}
+        assert lengths == set(io_model.EDGE_LENGTHS)
+        for op in everything:
+            assert op[1] % 512 == 0 and op[1] % 4096 != 0
+            assert op[1] + io_model.op_length(op) <= size
+        assert io_model.op_tiles(("read", 0, 4608)) == 2
+        assert io_model.op_tiles(("write", 0, b"x" * 4096)) == 1
+        assert io_model.op_tiles(("flush",)) == 0
+
+
+class TestIoQueueCpu:
+    """hs.IoQueue, the model and the generator proven on the host-RAM
+    bdev: the same scenarios tests/test_engine_matrix.py runs on the
+    three HBM engines."""
+
+    @pytest.fixture
+    def rig(self):
+        import io_model
+        from oim_amd import _hipstore as hs
+
+        bdev = hs.create_malloc_bdev("ioq-cpu", 512, 131072)  # 64 MiB
+        queue = hs.IoQueue(bdev)
+        assert queue.kind == "cpu"
+        return bdev, queue, io_model.ByteModel(bdev.size_bytes)
+
+    def test_tile_edges(self, rig):
+        import io_model
+
+        bdev, queue, model = rig
+        assert io_model.scenario_tile_edges(queue, model, seed=1) == 82
+        assert bdev.read(0, bdev.size_bytes) == bytes(model.data)
+
+    def test_mixed_batch(self, rig):
+        import io_model
+
+        bdev, queue, model = rig
+        io_model.scenario_mixed_batch(queue, model, seed=2)
+        assert bdev.read(0, bdev.size_bytes) == bytes(model.data)
+
+    def test_results_shape(self, rig):
+        _, queue, _ = rig
+        assert queue.run([]) == []
+        payload = bytes(range(256)) * 2
+        assert queue.run([("write", 512, payload), ("flush",)]) == [
+            (0, None), (0, None)]
+        assert queue.run([("read", 512, 512), ("read", 1 << 40, 512),
+                          ("fill", 0, 512, 9)]) == [
+            (0, payload), (-22, None), (0, None)]
+        with pytest.raises(ValueError):
+            queue.run([("trim", 0, 512)])
+
+    def test_range_digest_ladder(self, rig):
+        """crc32c_gpu_range on the CPU fallback: the per-4 KiB CRC +
+        combine ladder against the bit-exact table over the bytes."""
+        from oim_amd import _hipstore as hs
+
+        bdev, queue, _ = rig
+        import random
+        data = random.Random(5).randbytes((1 << 20) + 8192)
+        queue.run([("write", 8192, data)])
+        for offset, length in ((8192, 4096), (8192, 8192),
+                               (12288, (1 << 20) + 4096)):
+            want = hs.crc32c_table(data[offset - 8192:offset - 8192 + length])
+            assert hs.crc32c_gpu_range(bdev, offset, length) == want
+        assert list(hs.crc32c_gpu_blocks(bdev, 8192, 512, 0)) == []
+        for bad_length in (0, 512, 4096 + 512):
+            with pytest.raises(RuntimeError):
+                hs.crc32c_gpu_range(bdev, 8192, bad_length)
