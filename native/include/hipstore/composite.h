@@ -29,4 +29,36 @@ BdevPtr create_striped_bdev(const std::string& name,
 BdevPtr create_replicated_bdev(const std::string& name,
                                std::vector<BdevPtr> children);
 
+// Replica scrub: compares every other child of a replicated bdev with
+// child 0 over the whole device (bdev_diff_sync, so HBM children are
+// compared on the GPU) and reports one entry per replica. Child 0, the
+// primary, is authoritative: the write path already treats a primary
+// failure as fatal and the replicas as followers.
+//
+// With `repair`, each replica's mismatching granules are then
+// overwritten from the primary (bdev_copy_marked_sync). A repair racing
+// a guest write could put stale primary data over a newer fan-out, so
+// repair is refused with kIoFailed while the bdev is claimed() (the
+// offline rule resize follows). A compare-only scrub is allowed at any
+// time and is advisory: in-flight mirrored writes may show up as
+// transient mismatches.
+//
+// `granule` 0 means the block size. status is kIoInvalid when `bdev` is
+// not a replicated bdev or the granule is invalid; replicas compared
+// before a failure stay in the result.
+struct ScrubReplica {
+  size_t child = 0;         // index among the children (>= 1)
+  uint64_t granules = 0;
+  uint64_t mismatched = 0;
+  uint64_t repaired = 0;    // granules copied from the primary
+  std::vector<uint64_t> first_mismatches;
+};
+struct ScrubResult {
+  int status = kIoOk;  // IoStatus
+  uint32_t granule = 0;
+  std::vector<ScrubReplica> replicas;
+};
+ScrubResult replicated_scrub(Bdev* bdev, bool repair, uint32_t granule,
+                             uint32_t max_report);
+
 }  // namespace hipstore

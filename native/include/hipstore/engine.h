@@ -74,6 +74,50 @@ void free_pinned(void* ptr);
 int hbm_copy_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
                   uint64_t dst_offset, uint64_t length);
 
+// Granule-wise compare of two bdev ranges (clone verify, replica scrub,
+// changed-block list). Bit g of the bitmap (word g/64, bit g%64) is set
+// iff granule g of `a` differs from granule g of `b` in at least one
+// byte; bits past the last granule are 0.
+//
+// When both bdevs are HBM-resident the compare runs on the GPU
+// (hipstore::k_diff_granules; across devices the kernel runs on a's
+// device and reads b over peer access). Every other pairing, and HBM
+// pairs without peer access, read both sides through bdev_read_sync in
+// chunks of at most 1 MiB and compare on the host; both paths give the
+// same bitmap.
+//
+// Returns kIoInvalid unless: length > 0; both bdevs share a block size;
+// `granule` is a multiple of that block size and of 16; offsets and
+// length are multiples of `granule`; both ranges are in bounds.
+struct DiffStats {
+  uint64_t granules = 0;    // granules compared
+  uint64_t mismatched = 0;  // popcount of the bitmap
+  // First max_report mismatching granule indices, ascending.
+  std::vector<uint64_t> first_mismatches;
+};
+int bdev_diff_sync(Bdev* a, uint64_t a_offset, Bdev* b, uint64_t b_offset,
+                   uint64_t length, uint32_t granule, uint32_t max_report,
+                   std::vector<uint64_t>* bitmap_out, DiffStats* stats);
+
+// Default extent for the two calls here ("to the end of the shorter
+// device"): min(size - offset) over both sides, rounded down to a
+// multiple of `granule`; 0 when an offset lies past its device.
+uint64_t bdev_common_length(Bdev* a, uint64_t a_offset, Bdev* b,
+                            uint64_t b_offset, uint32_t granule);
+
+// Copies the granules of [src_offset, +length) whose bit is set in
+// `bitmap` (bdev_diff_sync layout) to the same granule of dst; other
+// granules of dst are not written. Same validation and path selection
+// as bdev_diff_sync (hipstore::k_copy_marked on the GPU path); also
+// kIoInvalid when the bitmap is shorter than the range or the ranges
+// overlap in one backing store. `copied` receives the number of
+// granules copied.
+int bdev_copy_marked_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
+                          uint64_t dst_offset, uint64_t length,
+                          uint32_t granule,
+                          const std::vector<uint64_t>& bitmap,
+                          uint64_t* copied = nullptr);
+
 // Synchronous convenience wrappers (tests, NBD pump): create a
 // throwaway channel, submit, poll to completion. Returns IoStatus.
 int bdev_read_sync(Bdev* bdev, uint64_t offset, void* buf, uint64_t len);

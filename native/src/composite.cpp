@@ -439,4 +439,49 @@ BdevPtr create_replicated_bdev(const std::string& name,
   return std::make_shared<ReplicatedBdev>(name, std::move(children));
 }
 
+ScrubResult replicated_scrub(Bdev* bdev, bool repair, uint32_t granule,
+                             uint32_t max_report) {
+  ScrubResult result;
+  auto* replicated = dynamic_cast<ReplicatedBdev*>(bdev);
+  if (replicated == nullptr) {
+    result.status = kIoInvalid;
+    return result;
+  }
+  if (repair && bdev->claimed()) {
+    result.status = kIoFailed;
+    return result;
+  }
+  if (granule == 0) granule = static_cast<uint32_t>(bdev->block_size());
+  result.granule = granule;
+  const auto& children = replicated->children();
+  Bdev* primary = children[0].get();
+  // Whole device, rounded down to the granule: a trailing partial
+  // granule cannot be expressed in the bitmap.
+  const uint64_t length = primary->size_bytes() / granule * granule;
+  for (size_t i = 1; i < children.size(); ++i) {
+    ScrubReplica replica;
+    replica.child = i;
+    std::vector<uint64_t> bitmap;
+    DiffStats stats;
+    int status = bdev_diff_sync(primary, 0, children[i].get(), 0, length,
+                                granule, max_report, &bitmap, &stats);
+    if (status == kIoOk) {
+      replica.granules = stats.granules;
+      replica.mismatched = stats.mismatched;
+      replica.first_mismatches = std::move(stats.first_mismatches);
+      if (repair && stats.mismatched != 0) {
+        status = bdev_copy_marked_sync(primary, 0, children[i].get(), 0,
+                                       length, granule, bitmap,
+                                       &replica.repaired);
+      }
+    }
+    if (status != kIoOk) {
+      result.status = status;
+      return result;
+    }
+    result.replicas.push_back(std::move(replica));
+  }
+  return result;
+}
+
 }  // namespace hipstore

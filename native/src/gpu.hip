@@ -160,6 +160,93 @@ __global__ __launch_bounds__(256) void k_crc32c_blocks(
   out[idx] = ~crc;
 }
 
+// --- granule compare / marked copy (replica scrub, clone verify) -----------
+//
+// One workgroup owns one 64-bit bitmap word (64 granules) per
+// grid-stride step; each of its 4 waves compares 16 consecutive
+// granules, one whole granule at a time: 16 B/lane loads of both
+// sides, XOR, OR into a lane-private accumulator, then one 64-bit
+// ballot decides the granule's bit (wave-uniform). The four 16-bit
+// partials meet in LDS and thread 0 writes the word with one plain
+// store: no atomics, no pre-zeroed buffer, and tail bits past
+// n_granules are written as 0 because their granules are never
+// visited. Granules below 1 KiB leave the upper lanes idle.
+constexpr uint32_t kDiffGranulesPerWave = 64 / kWavesPerWg;
+
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_diff_granules(
+    const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+    uint64_t n_granules, uint32_t granule_bytes,
+    unsigned long long* __restrict__ bitmap) {
+  __shared__ uint32_t partial[kWavesPerWg];
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule_bytes >> 4;
+  const uint64_t n_words = (n_granules + 63) >> 6;
+  for (uint64_t w = blockIdx.x; w < n_words; w += gridDim.x) {
+    const uint64_t g0 = w * 64 + wave * kDiffGranulesPerWave;
+    uint32_t bits = 0;
+    for (uint32_t j = 0; j < kDiffGranulesPerWave; ++j) {
+      const uint64_t g = g0 + j;
+      if (g >= n_granules) break;  // wave-uniform
+      const uint4* __restrict__ pa =
+          reinterpret_cast<const uint4*>(a + g * granule_bytes);
+      const uint4* __restrict__ pb =
+          reinterpret_cast<const uint4*>(b + g * granule_bytes);
+      uint32_t acc = 0;
+#pragma unroll 4
+      for (uint32_t i = lane; i < n16; i += 64) {
+        const uint4 x = pa[i];
+        const uint4 y = pb[i];
+        acc |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+      }
+      if (__ballot(acc != 0) != 0ull) bits |= 1u << j;
+    }
+    if (lane == 0) partial[wave] = bits;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long word = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kWavesPerWg; ++k) {
+        word |= static_cast<unsigned long long>(partial[k])
+                << (k * kDiffGranulesPerWave);
+      }
+      bitmap[w] = word;
+    }
+    __syncthreads();  // partial[] is rewritten by the next step
+  }
+}
+
+// Copies exactly the granules whose bitmap bit is set. Same work split
+// as k_diff_granules (workgroup per word, wave per 16-bit slice, wave
+// per granule), so the bit test is wave-uniform and a zero word costs
+// one load. Unmarked granules of dst are never written.
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_copy_marked(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+    const unsigned long long* __restrict__ bitmap, uint64_t n_granules,
+    uint32_t granule_bytes) {
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule_bytes >> 4;
+  const uint64_t n_words = (n_granules + 63) >> 6;
+  for (uint64_t w = blockIdx.x; w < n_words; w += gridDim.x) {
+    const unsigned long long word = bitmap[w];
+    uint32_t bits = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(
+        (word >> (wave * kDiffGranulesPerWave)) & 0xFFFFu));
+    while (bits != 0) {
+      const uint32_t j = static_cast<uint32_t>(__builtin_ctz(bits));
+      bits &= bits - 1;
+      const uint64_t g = w * 64 + wave * kDiffGranulesPerWave + j;
+      if (g >= n_granules) break;  // stray tail bits in the caller's bitmap
+      const uint4* __restrict__ ps =
+          reinterpret_cast<const uint4*>(src + g * granule_bytes);
+      uint4* __restrict__ pd =
+          reinterpret_cast<uint4*>(dst + g * granule_bytes);
+#pragma unroll 4
+      for (uint32_t i = lane; i < n16; i += 64) pd[i] = ps[i];
+    }
+  }
+}
+
 // --- persistent service kernel ---------------------------------------------
 //
 // SPDK replaced kernel-driver queues with host polling reactors; the
@@ -2076,6 +2163,296 @@ int bdev_fill_sync(Bdev* bdev, uint64_t offset, uint8_t value, uint64_t len) {
   req.length = len;
   req.fill = value;
   return run_sync(bdev, std::move(req));
+}
+
+// ---------------------------------------------------------------------------
+// Granule compare / marked copy
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint64_t kDiffHostChunk = 1ull << 20;  // generic-path read size cap
+// 256 MiB of bitmap; keeps the pinned buffer and the host fold bounded.
+constexpr uint64_t kMaxDiffGranules = 1ull << 31;
+
+// Per-thread pinned buffers, grown on demand and kept: hipHostFree
+// waits for the device to go idle, which stalls behind resident service
+// kernels (see IoQueue::run), so nothing is freed per call. The GPU
+// writes / reads the bitmap in place (zero-copy; it is 1/4096 of the
+// data at 512-byte granules).
+struct DiffCtx {
+  unsigned long long* words = nullptr;
+  uint64_t capacity = 0;
+  uint8_t* scratch = nullptr;  // 2 x kDiffHostChunk, generic path
+
+  ~DiffCtx() {
+    free_pinned(words);
+    free_pinned(scratch);
+  }
+
+  unsigned long long* bitmap(uint64_t n_words) {
+    if (n_words > capacity) {
+      free_pinned(words);
+      words = nullptr;
+      capacity = 0;
+      const uint64_t want = std::max<uint64_t>(n_words, 4096);
+      words = static_cast<unsigned long long*>(alloc_pinned(want * 8));
+      if (words == nullptr) throw std::runtime_error("diff: out of memory");
+      capacity = want;
+    }
+    return words;
+  }
+
+  uint8_t* chunks() {
+    if (scratch == nullptr) {
+      scratch = static_cast<uint8_t*>(alloc_pinned(2 * kDiffHostChunk));
+      if (scratch == nullptr) throw std::runtime_error("diff: out of memory");
+    }
+    return scratch;
+  }
+};
+
+DiffCtx& diff_ctx() {
+  thread_local DiffCtx ctx;
+  return ctx;
+}
+
+// Shared validation. Bounds are phrased by subtraction so no 64-bit sum
+// can wrap.
+bool granule_ranges_ok(Bdev* a, uint64_t a_offset, Bdev* b, uint64_t b_offset,
+                       uint64_t length, uint32_t granule) {
+  if (a == nullptr || b == nullptr) return false;
+  const uint64_t bs = a->block_size();
+  if (bs == 0 || bs != b->block_size() || bs > kDiffHostChunk) return false;
+  if (granule == 0 || granule % bs != 0 || granule % 16 != 0) return false;
+  if (length == 0 || length % granule != 0 || a_offset % granule != 0 ||
+      b_offset % granule != 0) {
+    return false;
+  }
+  if (length > a->size_bytes() || a_offset > a->size_bytes() - length ||
+      length > b->size_bytes() || b_offset > b->size_bytes() - length) {
+    return false;
+  }
+  return length / granule <= kMaxDiffGranules;
+}
+
+// Device the pair's kernels run on, or -1 for the generic path: both
+// bdevs HBM-resident, and across devices `a`'s device must be able to
+// reach `b`'s memory (peer access, enabled as ReplicatedBdev does).
+int granule_kernel_device(Bdev* a, Bdev* b) {
+  if (a->device_base() == nullptr || b->device_base() == nullptr) return -1;
+  if (!gpu_available()) return -1;
+  const int a_dev = a->gpu_device();
+  const int b_dev = b->gpu_device();
+  if (a_dev < 0 || b_dev < 0) return -1;
+  if (a_dev == b_dev) return a_dev;
+  int can = 0;
+  if (hipSetDevice(a_dev) != hipSuccess ||
+      hipDeviceCanAccessPeer(&can, a_dev, b_dev) != hipSuccess || can == 0) {
+    return -1;
+  }
+  const hipError_t err = hipDeviceEnablePeerAccess(b_dev, 0);
+  (void)hipGetLastError();  // "already enabled" must not stick
+  if (err != hipSuccess && err != hipErrorPeerAccessAlreadyEnabled) return -1;
+  return a_dev;
+}
+
+// Own stream, one launch, synchronise (hbm_copy_sync style).
+template <typename Launch>
+int run_granule_kernel(int device, Launch launch) {
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = nullptr;
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    // Polling elsewhere on this thread leaves hipErrorNotReady behind;
+    // only a failure of this launch may fail the call.
+    (void)hipGetLastError();
+    launch(stream);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
+    return err == hipSuccess ? kIoOk : kIoFailed;
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
+}
+
+uint32_t granule_grid(uint64_t n_granules) {
+  return static_cast<uint32_t>(
+      std::min<uint64_t>((n_granules + 63) / 64, 2048));
+}
+
+// Largest multiple of the block size that fits the generic-path cap.
+uint64_t host_chunk_bytes(Bdev* bdev) {
+  return kDiffHostChunk / bdev->block_size() * bdev->block_size();
+}
+
+int diff_generic(Bdev* a, uint64_t a_offset, Bdev* b, uint64_t b_offset,
+                 uint64_t length, uint32_t granule,
+                 unsigned long long* words, uint64_t n_words) {
+  memset(words, 0, n_words * 8);
+  uint8_t* buf_a = diff_ctx().chunks();
+  uint8_t* buf_b = buf_a + kDiffHostChunk;
+  const uint64_t chunk = host_chunk_bytes(a);
+  for (uint64_t pos = 0; pos < length; pos += chunk) {
+    const uint64_t n = std::min(chunk, length - pos);
+    int status = bdev_read_sync(a, a_offset + pos, buf_a, n);
+    if (status == kIoOk) status = bdev_read_sync(b, b_offset + pos, buf_b, n);
+    if (status != kIoOk) return status;
+    // A chunk need not start or end on a granule boundary (granules
+    // above the cap span several chunks): compare piecewise.
+    for (uint64_t off = 0; off < n;) {
+      const uint64_t g = (pos + off) / granule;
+      const uint64_t piece =
+          std::min<uint64_t>(granule - (pos + off) % granule, n - off);
+      if (memcmp(buf_a + off, buf_b + off, piece) != 0) {
+        words[g / 64] |= 1ull << (g % 64);
+      }
+      off += piece;
+    }
+  }
+  return kIoOk;
+}
+
+int copy_span_generic(Bdev* src, uint64_t src_offset, Bdev* dst,
+                      uint64_t dst_offset, uint64_t length) {
+  uint8_t* buf = diff_ctx().chunks();
+  const uint64_t chunk = host_chunk_bytes(src);
+  for (uint64_t pos = 0; pos < length; pos += chunk) {
+    const uint64_t n = std::min(chunk, length - pos);
+    int status = bdev_read_sync(src, src_offset + pos, buf, n);
+    if (status == kIoOk) status = bdev_write_sync(dst, dst_offset + pos, buf, n);
+    if (status != kIoOk) return status;
+  }
+  return kIoOk;
+}
+
+inline bool bitmap_test(const std::vector<uint64_t>& bitmap, uint64_t g) {
+  return (bitmap[g / 64] >> (g % 64)) & 1;
+}
+
+}  // namespace
+
+uint64_t bdev_common_length(Bdev* a, uint64_t a_offset, Bdev* b,
+                            uint64_t b_offset, uint32_t granule) {
+  if (granule == 0 || a_offset > a->size_bytes() ||
+      b_offset > b->size_bytes()) {
+    return 0;
+  }
+  const uint64_t room =
+      std::min(a->size_bytes() - a_offset, b->size_bytes() - b_offset);
+  return room / granule * granule;
+}
+
+int bdev_diff_sync(Bdev* a, uint64_t a_offset, Bdev* b, uint64_t b_offset,
+                   uint64_t length, uint32_t granule, uint32_t max_report,
+                   std::vector<uint64_t>* bitmap_out, DiffStats* stats) {
+  if (!granule_ranges_ok(a, a_offset, b, b_offset, length, granule)) {
+    return kIoInvalid;
+  }
+  const uint64_t n_granules = length / granule;
+  const uint64_t n_words = (n_granules + 63) / 64;
+  unsigned long long* words = nullptr;
+  int status;
+  try {
+    words = diff_ctx().bitmap(n_words);
+    const int device = granule_kernel_device(a, b);
+    if (device >= 0) {
+      unsigned long long* dev_words = device_view(words);
+      const uint8_t* pa = static_cast<uint8_t*>(a->device_base()) + a_offset;
+      const uint8_t* pb = static_cast<uint8_t*>(b->device_base()) + b_offset;
+      status = run_granule_kernel(device, [&](hipStream_t stream) {
+        hipLaunchKernelGGL(k_diff_granules, dim3(granule_grid(n_granules)),
+                           dim3(kWavesPerWg * 64), 0, stream, pa, pb,
+                           n_granules, granule, dev_words);
+      });
+    } else {
+      status = diff_generic(a, a_offset, b, b_offset, length, granule, words,
+                            n_words);
+    }
+  } catch (const std::exception&) {
+    status = kIoFailed;
+  }
+  if (status != kIoOk) return status;
+  if (stats != nullptr) {
+    stats->granules = n_granules;
+    stats->mismatched = 0;
+    stats->first_mismatches.clear();
+    for (uint64_t w = 0; w < n_words; ++w) {
+      unsigned long long word = words[w];
+      stats->mismatched += static_cast<uint64_t>(__builtin_popcountll(word));
+      while (word != 0 && stats->first_mismatches.size() < max_report) {
+        stats->first_mismatches.push_back(
+            w * 64 + static_cast<uint64_t>(__builtin_ctzll(word)));
+        word &= word - 1;
+      }
+    }
+  }
+  if (bitmap_out != nullptr) bitmap_out->assign(words, words + n_words);
+  return kIoOk;
+}
+
+int bdev_copy_marked_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
+                          uint64_t dst_offset, uint64_t length,
+                          uint32_t granule,
+                          const std::vector<uint64_t>& bitmap,
+                          uint64_t* copied) {
+  if (!granule_ranges_ok(src, src_offset, dst, dst_offset, length, granule)) {
+    return kIoInvalid;
+  }
+  const uint64_t n_granules = length / granule;
+  const uint64_t n_words = (n_granules + 63) / 64;
+  if (bitmap.size() < n_words) return kIoInvalid;
+  // Overlap is only possible within one backing store (validated
+  // ranges: the differences below cannot wrap).
+  const uint8_t* s_base = static_cast<uint8_t*>(src->device_base());
+  const uint8_t* d_base = static_cast<uint8_t*>(dst->device_base());
+  const bool same_store =
+      src == dst || (s_base != nullptr && s_base == d_base &&
+                     src->gpu_device() == dst->gpu_device());
+  if (same_store) {
+    const uint64_t lo = std::min(src_offset, dst_offset);
+    const uint64_t hi = std::max(src_offset, dst_offset);
+    if (hi - lo < length) return kIoInvalid;
+  }
+  uint64_t marked = 0;
+  for (uint64_t g = 0; g < n_granules; ++g) marked += bitmap_test(bitmap, g);
+  if (copied != nullptr) *copied = 0;
+  if (marked == 0) return kIoOk;  // nothing to copy: no launch
+  int status = kIoOk;
+  try {
+    const int device = granule_kernel_device(src, dst);
+    if (device >= 0) {
+      unsigned long long* words = diff_ctx().bitmap(n_words);
+      for (uint64_t w = 0; w < n_words; ++w) words[w] = bitmap[w];
+      const unsigned long long* dev_words = device_view(words);
+      const uint8_t* ps = s_base + src_offset;
+      uint8_t* pd = static_cast<uint8_t*>(dst->device_base()) + dst_offset;
+      status = run_granule_kernel(device, [&](hipStream_t stream) {
+        hipLaunchKernelGGL(k_copy_marked, dim3(granule_grid(n_granules)),
+                           dim3(kWavesPerWg * 64), 0, stream, ps, pd,
+                           dev_words, n_granules, granule);
+      });
+    } else {
+      // Runs of marked granules move as one span.
+      for (uint64_t g = 0; g < n_granules && status == kIoOk;) {
+        if (!bitmap_test(bitmap, g)) {
+          ++g;
+          continue;
+        }
+        uint64_t end = g + 1;
+        while (end < n_granules && bitmap_test(bitmap, end)) ++end;
+        status = copy_span_generic(src, src_offset + g * granule, dst,
+                                   dst_offset + g * granule,
+                                   (end - g) * granule);
+        g = end;
+      }
+    }
+  } catch (const std::exception&) {
+    status = kIoFailed;
+  }
+  if (status == kIoOk && copied != nullptr) *copied = marked;
+  return status;
 }
 
 // ---------------------------------------------------------------------------

@@ -963,6 +963,120 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
     return Json(JsonObject{});
   });
 
+  // --- compare / scrub / repair (native extensions) ------------------------
+  // Shared param parsing: non-negative integers only, granule 0 = the
+  // block size, max_report capped.
+  auto uint_param = [](const Json& p, const char* key, int64_t dflt) {
+    const int64_t v = p.get_int(key, dflt);
+    if (v < 0) {
+      throw RpcError{kInvalidParams, std::string(key) + " must be >= 0"};
+    }
+    return static_cast<uint64_t>(v);
+  };
+  auto granule_param = [uint_param](const Json& p, const BdevPtr& bdev) {
+    const uint64_t granule = uint_param(p, "granule", 0);
+    if (granule > UINT32_MAX) {
+      throw RpcError{kInvalidParams, "granule too large"};
+    }
+    return granule == 0 ? static_cast<uint32_t>(bdev->block_size())
+                        : static_cast<uint32_t>(granule);
+  };
+  auto max_report_param = [uint_param](const Json& p) {
+    return static_cast<uint32_t>(
+        std::min<uint64_t>(uint_param(p, "max_report", 16), 1024));
+  };
+  auto indices_to_json = [](const std::vector<uint64_t>& indices) {
+    JsonArray out;
+    for (uint64_t g : indices) out.push_back(Json(static_cast<int64_t>(g)));
+    return Json(std::move(out));
+  };
+
+  server->register_method(
+      "bdev_compare",
+      [&manager, uint_param, granule_param, max_report_param,
+       indices_to_json](const Json& p) {
+        // Granule-wise compare of two bdev ranges: on the GPU for HBM
+        // pairs, through bdev reads otherwise (clone/snapshot verify,
+        // changed-block count).
+        BdevPtr a = manager.find(p.get_string("a"));
+        if (!a) not_found("bdev " + p.get_string("a"));
+        BdevPtr b = manager.find(p.get_string("b"));
+        if (!b) not_found("bdev " + p.get_string("b"));
+        const uint64_t a_offset = uint_param(p, "a_offset", 0);
+        const uint64_t b_offset = uint_param(p, "b_offset", 0);
+        const uint32_t granule = granule_param(p, a);
+        uint64_t length = uint_param(p, "length", 0);
+        if (!p.has("length")) {
+          length = bdev_common_length(a.get(), a_offset, b.get(), b_offset,
+                                      granule);
+        }
+        DiffStats stats;
+        const int status =
+            bdev_diff_sync(a.get(), a_offset, b.get(), b_offset, length,
+                           granule, max_report_param(p), nullptr, &stats);
+        if (status == kIoInvalid) {
+          throw RpcError{kInvalidParams,
+                         "bdev_compare: invalid range or granule (equal "
+                         "block sizes; granule a multiple of the block size "
+                         "and of 16; offsets and length multiples of the "
+                         "granule, in bounds, length > 0)"};
+        }
+        if (status != kIoOk) {
+          throw RpcError{kInternalError, "bdev_compare: I/O failed"};
+        }
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(granule));
+        o["granules"] = Json(static_cast<int64_t>(stats.granules));
+        o["mismatched"] = Json(static_cast<int64_t>(stats.mismatched));
+        o["first_mismatches"] = indices_to_json(stats.first_mismatches);
+        return Json(std::move(o));
+      });
+
+  server->register_method(
+      "bdev_replica_scrub",
+      [&manager, granule_param, max_report_param,
+       indices_to_json](const Json& p) {
+        // Compare every replica with child 0; with repair, overwrite
+        // the mismatching granules from it. Repair is offline-only.
+        const std::string name = p.get_string("name");
+        BdevPtr bdev = manager.find(name);
+        if (!bdev) not_found("bdev " + name);
+        const bool repair = p.get_bool("repair", false);
+        const uint32_t granule = granule_param(p, bdev);
+        if (repair && bdev->claimed()) {
+          throw RpcError{kInternalError,
+                         "bdev " + name +
+                             " is claimed; repair runs offline only (a "
+                             "compare-only scrub is allowed)"};
+        }
+        const ScrubResult r = replicated_scrub(bdev.get(), repair, granule,
+                                               max_report_param(p));
+        if (r.status == kIoInvalid) {
+          throw RpcError{kInvalidParams,
+                         "bdev " + name +
+                             " is not a replicated bdev, or the granule is "
+                             "not a multiple of the block size and of 16"};
+        }
+        if (r.status != kIoOk) {
+          throw RpcError{kInternalError,
+                         "bdev_replica_scrub: I/O failed or bdev claimed"};
+        }
+        JsonArray replicas;
+        for (const ScrubReplica& rep : r.replicas) {
+          JsonObject o;
+          o["child"] = Json(static_cast<int64_t>(rep.child));
+          o["granules"] = Json(static_cast<int64_t>(rep.granules));
+          o["mismatched"] = Json(static_cast<int64_t>(rep.mismatched));
+          o["repaired"] = Json(static_cast<int64_t>(rep.repaired));
+          o["first_mismatches"] = indices_to_json(rep.first_mismatches);
+          replicas.push_back(Json(std::move(o)));
+        }
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(r.granule));
+        o["replicas"] = Json(std::move(replicas));
+        return Json(std::move(o));
+      });
+
   // Stepped benchmarking with persistent queues (bench.py contract):
   // perf_session_start -> id; perf_session_step runs a fixed I/O count
   // on the session's live queues; perf_session_stop tears down.

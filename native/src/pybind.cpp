@@ -291,6 +291,109 @@ PYBIND11_MODULE(_hipstore, m) {
      "Device-side range copy between HBM bdevs (LDS-staged kernel "
      "same-device, xGMI peer copy cross-device)");
 
+  m.def("bdev_diff", [](BdevPtr a, BdevPtr b, uint64_t a_offset,
+                        uint64_t b_offset, uint64_t length, uint32_t granule,
+                        uint32_t max_report) {
+    if (granule == 0) granule = static_cast<uint32_t>(a->block_size());
+    if (length == 0) length = bdev_common_length(a.get(), a_offset, b.get(),
+                                                     b_offset, granule);
+    std::vector<uint64_t> bitmap;
+    DiffStats stats;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_diff_sync(a.get(), a_offset, b.get(), b_offset, length,
+                              granule, max_report, &bitmap, &stats);
+    }
+    if (status != kIoOk) {
+      throw std::runtime_error("bdev_diff failed: status " +
+                               std::to_string(status));
+    }
+    // Little-endian bytes: granule g is byte g//8, bit g%8.
+    const size_t n_bytes = (stats.granules + 7) / 8;
+    std::string raw(n_bytes, '\0');
+    for (size_t i = 0; i < n_bytes; ++i) {
+      raw[i] = static_cast<char>((bitmap[i / 8] >> (8 * (i % 8))) & 0xFF);
+    }
+    py::dict d;
+    d["granules"] = stats.granules;
+    d["mismatched"] = stats.mismatched;
+    d["first_mismatches"] = stats.first_mismatches;
+    d["bitmap"] = py::bytes(raw);
+    return d;
+  }, py::arg("a"), py::arg("b"), py::arg("a_offset") = 0,
+     py::arg("b_offset") = 0, py::arg("length") = 0, py::arg("granule") = 0,
+     py::arg("max_report") = 16,
+     "Granule-wise compare of two bdev ranges (on-GPU for HBM pairs). "
+     "length=0: up to the end of the shorter device; granule=0: the "
+     "block size");
+
+  m.def("bdev_copy_marked", [](BdevPtr src, BdevPtr dst, py::bytes bitmap,
+                               uint32_t granule, uint64_t src_offset,
+                               uint64_t dst_offset, uint64_t length) {
+    if (granule == 0) granule = static_cast<uint32_t>(src->block_size());
+    if (length == 0) length = bdev_common_length(src.get(), src_offset, dst.get(),
+                                                     dst_offset, granule);
+    const std::string raw = bitmap;
+    const uint64_t n_granules = length / granule;
+    if (raw.size() < n_granules / 8 + (n_granules % 8 != 0)) {
+      throw std::runtime_error("bdev_copy_marked: bitmap shorter than range");
+    }
+    std::vector<uint64_t> words((raw.size() + 7) / 8, 0);
+    for (size_t i = 0; i < raw.size(); ++i) {
+      words[i / 8] |= static_cast<uint64_t>(static_cast<uint8_t>(raw[i]))
+                      << (8 * (i % 8));
+    }
+    uint64_t copied = 0;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_copy_marked_sync(src.get(), src_offset, dst.get(),
+                                     dst_offset, length, granule, words,
+                                     &copied);
+    }
+    if (status != kIoOk) {
+      throw std::runtime_error("bdev_copy_marked failed: status " +
+                               std::to_string(status));
+    }
+    return copied;
+  }, py::arg("src"), py::arg("dst"), py::arg("bitmap"), py::arg("granule"),
+     py::arg("src_offset") = 0, py::arg("dst_offset") = 0,
+     py::arg("length") = 0,
+     "Copy only the granules marked in `bitmap` (bdev_diff layout); "
+     "returns the number copied");
+
+  m.def("replica_scrub", [](BdevPtr bdev, bool repair, uint32_t granule,
+                            uint32_t max_report) {
+    ScrubResult r;
+    {
+      py::gil_scoped_release release;
+      r = replicated_scrub(bdev.get(), repair, granule, max_report);
+    }
+    if (r.status != kIoOk) {
+      throw std::runtime_error("replica_scrub failed: status " +
+                               std::to_string(r.status));
+    }
+    py::list replicas;
+    for (const ScrubReplica& rep : r.replicas) {
+      py::dict d;
+      d["child"] = rep.child;
+      d["granules"] = rep.granules;
+      d["mismatched"] = rep.mismatched;
+      d["repaired"] = rep.repaired;
+      d["first_mismatches"] = rep.first_mismatches;
+      replicas.append(d);
+    }
+    py::dict out;
+    out["granule"] = r.granule;
+    out["replicas"] = replicas;
+    return out;
+  }, py::arg("bdev"), py::arg("repair") = false, py::arg("granule") = 0,
+     py::arg("max_report") = 16,
+     "Compare every replica of a replicated bdev with child 0; with "
+     "repair, overwrite mismatching granules from it (refused while the "
+     "bdev is claimed)");
+
   m.def("persistent_probe", &persistent_probe, py::arg("device") = 0,
         py::arg("flags") = 1,
         py::call_guard<py::gil_scoped_release>());

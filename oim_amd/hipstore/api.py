@@ -233,6 +233,45 @@ def bdev_clone(client: Client, src: str, name: str) -> str:
     return client.invoke("bdev_clone", {"src": src, "name": name})
 
 
+def bdev_compare(client: Client, a: str, b: str, a_offset: int = 0,
+                 b_offset: int = 0, length: Optional[int] = None,
+                 granule: Optional[int] = None,
+                 max_report: Optional[int] = None) -> Dict:
+    """Granule-wise compare of two bdev ranges (on-GPU for HBM pairs).
+
+    Returns {granule, granules, mismatched, first_mismatches}. length
+    defaults to the end of the shorter device, granule to the block
+    size."""
+    params: Dict = {"a": a, "b": b}
+    if a_offset:
+        params["a_offset"] = a_offset
+    if b_offset:
+        params["b_offset"] = b_offset
+    if length is not None:
+        params["length"] = length
+    if granule is not None:
+        params["granule"] = granule
+    if max_report is not None:
+        params["max_report"] = max_report
+    return client.invoke("bdev_compare", params)
+
+
+def bdev_replica_scrub(client: Client, name: str, repair: bool = False,
+                       granule: Optional[int] = None,
+                       max_report: Optional[int] = None) -> Dict:
+    """Compare every replica of a replicated bdev with child 0; with
+    repair (offline only) overwrite the mismatching granules from it.
+
+    Returns {granule, replicas: [{child, granules, mismatched, repaired,
+    first_mismatches}]}."""
+    params: Dict = {"name": name, "repair": repair}
+    if granule is not None:
+        params["granule"] = granule
+    if max_report is not None:
+        params["max_report"] = max_report
+    return client.invoke("bdev_replica_scrub", params)
+
+
 def resize_malloc_bdev(client: Client, name: str, size: int) -> int:
     """Offline resize to `size` bytes; returns the new block count."""
     return client.invoke("resize_malloc_bdev",

@@ -40,7 +40,8 @@ def fuzz_config(examples: int) -> None:
     entry = st.fixed_dictionaries({}, optional={
         "method": st.one_of(scalar, st.sampled_from(
             ["construct_malloc_bdev", "construct_aio_bdev", "bdev_clone",
-             "bdev_copy", "resize_malloc_bdev", "save_config",
+             "bdev_copy", "bdev_compare", "bdev_replica_scrub",
+             "resize_malloc_bdev", "save_config",
              "load_config", "construct_striped_malloc_bdev", "no_such"])),
         "params": st.one_of(scalar, st.dictionaries(
             st.sampled_from(["name", "num_blocks", "block_size", "src",
