@@ -273,6 +273,29 @@ __device__ __forceinline__ unsigned long long wave_bcast_u64(
          static_cast<uint32_t>(lo);
 }
 
+// Bounded CAS claim, shared by both resident kernels: take index `c`
+// of a ring only while the leader has published work past it
+// (`c < kt`, claim-only-when-available). The original blind
+// fetch_add-then-wait form wedged the serving wave on current pool
+// firmware (round-2 diagnosis, tools/engine_diag*.sh), and in the
+// shared service it would park a worker on one ring while others have
+// work. Lane 0 does the CAS, the wave follows its result. Returns the
+// claimed index, or ~0 when the ring has nothing left.
+__device__ __forceinline__ unsigned long long claim_bounded(
+    unsigned long long* counter, unsigned long long c,
+    unsigned long long kt, uint32_t lane) {
+  while (c < kt) {
+    unsigned long long witnessed = 0;
+    if (lane == 0) {
+      witnessed = atomicCAS(counter, c, c + 1);
+    }
+    witnessed = wave_bcast_u64(witnessed);
+    if (witnessed == c) return c;
+    c = witnessed;
+  }
+  return ~0ull;
+}
+
 struct PersistentCtl {
   // Pinned host memory (GPU reads/writes over PCIe, uncached):
   const BlockDesc* sq;     // descriptor ring
@@ -327,29 +350,12 @@ __global__ __launch_bounds__(64) void k_persistent_copy(PersistentCtl ctl) {
   }
 
   while (true) {
-    // Bounded CAS claim: take a descriptor index only when the leader
-    // has published work past it (claim-only-when-available, the
-    // shared-service discipline). The original blind
-    // fetch_add-then-wait form wedged the serving wave on current
-    // pool firmware (round-2 diagnosis, tools/engine_diag*.sh) while
-    // this form is proven on the same boxes by k_shared_service.
     const unsigned long long kt = __hip_atomic_load(
         ctl.known_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long c = __hip_atomic_load(
+    const unsigned long long c = __hip_atomic_load(
         ctl.claim_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long claim = ~0ull;
-    while (c < kt) {
-      unsigned long long witnessed = 0;
-      if (lane == 0) {
-        witnessed = atomicCAS(ctl.claim_counter, c, c + 1);
-      }
-      witnessed = wave_bcast_u64(witnessed);
-      if (witnessed == c) {
-        claim = c;
-        break;
-      }
-      c = witnessed;
-    }
+    const unsigned long long claim =
+        claim_bounded(ctl.claim_counter, c, kt, lane);
     if (claim == ~0ull) {
       if (__hip_atomic_load(ctl.exit_flag, __ATOMIC_RELAXED,
                             __HIP_MEMORY_SCOPE_AGENT) != 0) {
@@ -552,20 +558,9 @@ __global__ __launch_bounds__(64) void k_shared_service(SharedCtl ctl) {
       if (!(ma >> 32)) continue;
       const uint32_t ring_mask = static_cast<uint32_t>(ma);
       const unsigned long long kt = slot_ld(slot, 4);
-      unsigned long long c = slot_ld(slot, 3);
-      unsigned long long claim = ~0ull;
-      while (c < kt) {
-        unsigned long long witnessed = 0;
-        if (lane == 0) {
-          witnessed = atomicCAS(&slot->claim, c, c + 1);
-        }
-        witnessed = wave_bcast_u64(witnessed);
-        if (witnessed == c) {
-          claim = c;
-          break;
-        }
-        c = witnessed;
-      }
+      const unsigned long long c = slot_ld(slot, 3);
+      const unsigned long long claim =
+          claim_bounded(&slot->claim, c, kt, lane);
       if (claim == ~0ull) continue;
       // Serve it (volatile loads: pinned after the claim, never hoisted).
       const BlockDesc* sq = reinterpret_cast<const BlockDesc*>(slot_ld(slot, 0));
@@ -853,15 +848,72 @@ T* device_view(T* host_ptr) {
   return reinterpret_cast<T*>(dev);
 }
 
-// Engine channels tag their kind so HbmBdev can dispatch without
-// RTTI in the hot path (channels of different kinds coexist on one
-// bdev when the auto-fallback kicks in).
+// What HbmBdev needs from an engine channel. Channels of different
+// engines coexist on one bdev when the auto-fallback kicks in, so the
+// bdev only ever talks to this interface.
 class HbmChannelBase : public IoChannel {
  public:
-  enum class Kind { kBatched, kPersistent, kShared };
-  explicit HbmChannelBase(Kind kind) : kind(kind) {}
-  const Kind kind;
+  // Queue a request; `status` != kIoOk completes it with that status
+  // from the next poll() without touching the GPU.
+  virtual void enqueue(IoRequest req, int status) = 0;
+  // Drive completions; returns the number completed. Every channel is
+  // polled through ITS OWN engine's poll(): a persistent bdev hands
+  // out batched/shared channels past the per-queue cap, and polling
+  // those through bdev-level flags cast them to the wrong class
+  // (round-1's "mixed-engine wedge": the misdispatched poll read
+  // garbage — stalled batched fallbacks, segfaulted shared ones —
+  // while the GPU side was healthy all along). The resident engines'
+  // polls make no HIP API calls on their hot path: poll() runs in a
+  // tight loop on every submitter thread, and even hipSetDevice takes
+  // the runtime's global lock — 4+ spinning threads convoyed on it
+  // and starved each other.
+  virtual int poll() = 0;
+  // "batched", "persistent" or "shared" (IoQueue::kind).
+  virtual const char* kind_name() const = 0;
 };
+
+// Bdev's interface passes channels as IoChannel*. Every channel an
+// HbmBdev hands out derives from HbmChannelBase, so this is the one
+// downcast of the engine; what kind of channel it is stays virtual.
+inline HbmChannelBase* hbm_channel(IoChannel* ch) {
+  return static_cast<HbmChannelBase*>(ch);
+}
+
+// The caller's buffer may be pinned (device-visible) or pageable.
+// Pinned path: translate; pageable would need a bounce buffer — the
+// daemon and bench always use alloc_pinned, so reject pageable here.
+uint8_t* buf_device(uint8_t* host) {
+  void* dev = nullptr;
+  hipError_t err = hipHostGetDevicePointer(&dev, host, 0);
+  if (err != hipSuccess) {
+    throw std::runtime_error(
+        "hipstore: I/O buffer is not pinned host memory (use alloc_pinned)");
+  }
+  return static_cast<uint8_t*>(dev);
+}
+
+// Requests are split into <=4 KiB tiles, one descriptor each.
+inline uint32_t tile_count(uint64_t length) {
+  return static_cast<uint32_t>((length + kTileBytes - 1) / kTileBytes);
+}
+
+// Descriptor for the `bytes`-long tile at byte `done` of a read, write
+// or fill request against the backing store at `base`.
+void fill_desc(BlockDesc& d, const IoRequest& req, uint8_t* base,
+               uint64_t done, uint32_t bytes) {
+  if (req.op == IoOp::kRead) {
+    d.src = base + req.offset + done;
+    d.dst = buf_device(static_cast<uint8_t*>(req.buffer) + done);
+  } else if (req.op == IoOp::kWrite) {
+    d.src = buf_device(static_cast<uint8_t*>(req.buffer) + done);
+    d.dst = base + req.offset + done;
+  } else {  // kFill
+    d.src = nullptr;
+    d.dst = base + req.offset + done;
+  }
+  d.bytes = bytes;
+  d.fill = req.fill;
+}
 
 struct PendingIo {
   IoRequest req;
@@ -877,7 +929,7 @@ struct InflightBatch {
 class HbmChannel : public HbmChannelBase {
  public:
   HbmChannel(int device, uint8_t* base, uint64_t size)
-      : HbmChannelBase(Kind::kBatched), base_(base), size_(size) {
+      : base_(base), size_(size) {
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ring_),
@@ -900,10 +952,25 @@ class HbmChannel : public HbmChannelBase {
     (void)hipStreamDestroy(stream_);
   }
 
-  void enqueue(IoRequest req, int status) {
+  const char* kind_name() const override { return "batched"; }
+
+  void enqueue(IoRequest req, int status) override {
     pending_.push_back(PendingIo{std::move(req), status});
   }
 
+  int poll() override {
+    int completed = retire(/*wait=*/false);
+    if (!pending_.empty()) {
+      // Launches must come from the bdev's device; only pay the
+      // runtime call when there is something to launch.
+      (void)hipSetDevice(device_);
+      kick();
+      completed += retire(/*wait=*/false);
+    }
+    return completed;
+  }
+
+ private:
   // Launch every pending request as one batch (if ring space allows).
   // Batches occupy CONTIGUOUS descriptor-ring slots [head, head+n) — the
   // kernel takes a flat pointer — so a batch never wraps: it is capped
@@ -922,8 +989,7 @@ class HbmChannel : public HbmChannelBase {
     for (const PendingIo& io : pending_) {
       uint32_t tiles = 0;
       if (io.status == kIoOk && io.req.op != IoOp::kFlush) {
-        tiles = static_cast<uint32_t>(
-            (io.req.length + kTileBytes - 1) / kTileBytes);
+        tiles = tile_count(io.req.length);
       }
       if (n + tiles > cap) break;
       n += tiles;
@@ -971,46 +1037,17 @@ class HbmChannel : public HbmChannelBase {
     return completed;
   }
 
-  bool idle() const { return pending_.empty() && inflight_.empty(); }
-  bool has_pending() const { return !pending_.empty(); }
-
- private:
   void expand(const IoRequest& req, uint32_t* slot) {
-    // Split a request into <=4 KiB tiles, one ring descriptor each.
-    // kick() capped the batch so [ring_head_, ring_head_+n) never wraps.
+    // One ring descriptor per tile. kick() capped the batch so
+    // [ring_head_, ring_head_+n) never wraps.
     uint64_t done = 0;
     while (done < req.length) {
       const uint32_t bytes = static_cast<uint32_t>(
           std::min<uint64_t>(kTileBytes, req.length - done));
-      BlockDesc& d = ring_[*slot];
-      if (req.op == IoOp::kRead) {
-        d.src = base_ + req.offset + done;
-        d.dst = buf_device(static_cast<uint8_t*>(req.buffer) + done);
-      } else if (req.op == IoOp::kWrite) {
-        d.src = buf_device(static_cast<uint8_t*>(req.buffer) + done);
-        d.dst = base_ + req.offset + done;
-      } else {  // kFill
-        d.src = nullptr;
-        d.dst = base_ + req.offset + done;
-      }
-      d.bytes = bytes;
-      d.fill = req.fill;
+      fill_desc(ring_[*slot], req, base_, done, bytes);
       ++*slot;
       done += bytes;
     }
-  }
-
-  // The caller's buffer may be pinned (device-visible) or pageable.
-  // Pinned path: translate; pageable would need a bounce buffer — the
-  // daemon and bench always use alloc_pinned, so reject pageable here.
-  uint8_t* buf_device(uint8_t* host) {
-    void* dev = nullptr;
-    hipError_t err = hipHostGetDevicePointer(&dev, host, 0);
-    if (err != hipSuccess) {
-      throw std::runtime_error(
-          "hipstore: I/O buffer is not pinned host memory (use alloc_pinned)");
-    }
-    return static_cast<uint8_t*>(dev);
   }
 
   hipEvent_t get_event() {
@@ -1035,6 +1072,181 @@ class HbmChannel : public HbmChannelBase {
   std::vector<PendingIo> pending_;
   std::deque<InflightBatch> inflight_;
   std::vector<hipEvent_t> event_pool_;
+};
+
+// Host side of a ring served by a RESIDENT kernel: the pinned
+// submission ring (SQ), its tail word and the completion ring (CQ), the
+// request bookkeeping around them, and the poll loop. The two resident
+// engines derive from it and differ only in who runs the GPU side:
+// HbmPersistentChannel launches a service kernel of its own,
+// HbmSharedChannel registers the rings with the per-device
+// SharedService.
+class ServiceRingChannel : public HbmChannelBase {
+ public:
+  static constexpr uint32_t kRing = 32768;  // descriptors (>= 2x max request tiles)
+
+  void enqueue(IoRequest req, int status) override {
+    if (status != kIoOk) {
+      immediate_.emplace_back(std::move(req.on_complete), status);
+      return;
+    }
+    if (req.op == IoOp::kFlush) {
+      flushes_.push_back({tail_, std::move(req.on_complete)});
+      return;
+    }
+    pending_.push_back(std::move(req));
+    drain_pending();
+  }
+
+  int poll() override {
+    int completed = 0;
+    // Swap out the immediate list before firing: a completion callback
+    // may resubmit, and a failed resubmission appends to immediate_
+    // again — mutating the vector mid-iteration.
+    if (!immediate_.empty()) {
+      auto batch = std::move(immediate_);
+      immediate_.clear();
+      for (auto& [cb, status] : batch) {
+        if (cb) cb(status);
+        ++completed;
+      }
+    }
+    // Retire the contiguous completed prefix of the CQ.
+    const uint64_t retired_from = completed_;
+    while (completed_ < tail_) {
+      unsigned long long seq = __atomic_load_n(
+          const_cast<const unsigned long long*>(&cq_[completed_ % kRing]),
+          __ATOMIC_ACQUIRE);
+      if (seq != completed_ + 1) break;
+      IoState* state = desc_io_[completed_ % kRing];
+      desc_io_[completed_ % kRing] = nullptr;
+      ++completed_;
+      if (state != nullptr && --state->remaining == 0) {
+        if (state->cb) state->cb(state->status);
+        delete state;
+        ++completed;
+      }
+    }
+    if (completed_ != retired_from) on_retired(completed_);
+    // Flush markers complete once their submission point is retired.
+    while (!flushes_.empty() && flushes_.front().first <= completed_) {
+      if (flushes_.front().second) flushes_.front().second(kIoOk);
+      flushes_.pop_front();
+      ++completed;
+    }
+    drain_pending();
+    if (completed > 0) last_progress_ = std::chrono::steady_clock::now();
+    // Liveness: if work is outstanding but nothing completed for a
+    // while, the service kernel may have idle-exited in the submit
+    // race window — on_stall() restarts it from the completed prefix
+    // (descriptor replay is idempotent). The 1 ms stall gate keeps
+    // on_stall()'s locked runtime calls (hipStreamQuery) out of the hot
+    // path: unthrottled, 8 polling threads serialized on them and
+    // collapsed throughput.
+    if (completed_ < tail_) {
+      const auto now = std::chrono::steady_clock::now();
+      if (now - last_progress_ > std::chrono::milliseconds(1)) {
+        on_stall();
+        last_progress_ = now;  // gate on_stall itself to 1/ms
+      }
+    }
+    return completed;
+  }
+
+ protected:
+  explicit ServiceRingChannel(uint8_t* base) : base_(base) {}
+
+  // The rings outlive this class's destructor on purpose: whether they
+  // may be freed depends on whether the GPU side is known to be done
+  // with them, which only the derived destructors can tell. Those call
+  // free_rings() and delete_unfired() at the points their teardown
+  // order needs.
+  ~ServiceRingChannel() override = default;
+
+  // The completed prefix advanced to `completed`.
+  virtual void on_retired(uint64_t /*completed*/) {}
+  // Work is outstanding and nothing completed for over 1 ms: make sure
+  // the service kernel is running.
+  virtual void on_stall() = 0;
+
+  // Pinned mapped SQ, tail word and CQ, zeroed. The caller has selected
+  // the device.
+  void alloc_rings() {
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sq_),
+                            kRing * sizeof(BlockDesc), hipHostMallocMapped));
+    void* p_tail = nullptr;
+    void* p_cq = nullptr;
+    HIP_CHECK(hipHostMalloc(&p_tail, 8, hipHostMallocMapped));
+    HIP_CHECK(hipHostMalloc(&p_cq, kRing * 8, hipHostMallocMapped));
+    sq_tail_ = static_cast<volatile unsigned long long*>(p_tail);
+    cq_ = static_cast<volatile unsigned long long*>(p_cq);
+    *sq_tail_ = 0;
+    memset(const_cast<unsigned long long*>(cq_), 0, kRing * 8);
+    desc_io_.resize(kRing, nullptr);
+  }
+
+  void free_rings() {
+    (void)hipHostFree(sq_);
+    (void)hipHostFree(const_cast<unsigned long long*>(sq_tail_));
+    (void)hipHostFree(const_cast<unsigned long long*>(cq_));
+  }
+
+  // Unfired completion callbacks (wedge teardown, undrained multi-tile
+  // IOs): delete, never call, so their captures are released without
+  // touching torn state.
+  void delete_unfired() {
+    std::set<IoState*> leftovers(desc_io_.begin(), desc_io_.end());
+    for (IoState* state : leftovers) delete state;
+  }
+
+  BlockDesc* sq_ = nullptr;
+  volatile unsigned long long* sq_tail_ = nullptr;
+  volatile unsigned long long* cq_ = nullptr;
+  uint64_t tail_ = 0;
+  uint64_t completed_ = 0;
+  std::chrono::steady_clock::time_point last_progress_{};
+
+ private:
+  // One per request; shared by the descriptors of all its tiles.
+  struct IoState {
+    IoCompletion cb;
+    uint32_t remaining;
+    int status;
+  };
+
+  bool has_capacity(uint32_t tiles) const {
+    return tail_ - completed_ + tiles <= kRing;
+  }
+
+  void drain_pending() {
+    while (!pending_.empty()) {
+      IoRequest& req = pending_.front();
+      const uint32_t tiles = tile_count(req.length);
+      if (!has_capacity(tiles)) return;
+      auto* state = new IoState{std::move(req.on_complete), tiles, kIoOk};
+      uint64_t done = 0;
+      uint64_t t = tail_;
+      while (done < req.length) {
+        const uint32_t bytes = static_cast<uint32_t>(
+            std::min<uint64_t>(kTileBytes, req.length - done));
+        fill_desc(sq_[t % kRing], req, base_, done, bytes);
+        desc_io_[t % kRing] = state;
+        ++t;
+        done += bytes;
+      }
+      tail_ = t;
+      // Publish: descriptors before the tail, release order.
+      __atomic_store_n(const_cast<unsigned long long*>(sq_tail_), tail_,
+                       __ATOMIC_RELEASE);
+      pending_.pop_front();
+    }
+  }
+
+  uint8_t* base_;
+  std::vector<IoState*> desc_io_;
+  std::deque<IoRequest> pending_;
+  std::deque<std::pair<uint64_t, IoCompletion>> flushes_;
+  std::vector<std::pair<IoCompletion, int>> immediate_;
 };
 
 // Host side of the persistent service kernel. One instance per channel.
@@ -1064,9 +1276,8 @@ inline bool fallback_is_shared() {
   return shared;
 }
 
-class HbmPersistentChannel : public HbmChannelBase {
+class HbmPersistentChannel : public ServiceRingChannel {
  public:
-  static constexpr uint32_t kRing = 32768;      // descriptors (>= 2x max request tiles)
   static constexpr uint32_t kIdleSpins = 500000;  // ~1 s of s_sleep polling
 
   // Worker waves per queue (1-wave workgroups). 16 default; QD-deep
@@ -1081,30 +1292,20 @@ class HbmPersistentChannel : public HbmChannelBase {
   }
 
   HbmPersistentChannel(int device, uint8_t* base)
-      : HbmChannelBase(Kind::kPersistent), base_(base), device_(device) {
+      : ServiceRingChannel(base), device_(device) {
     // The creator (HbmBdev::get_channel) claimed the per-device slot
     // with fetch_add BEFORE constructing; release it in the dtor.
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sq_),
-                            kRing * sizeof(BlockDesc), hipHostMallocMapped));
-    void* p_tail = nullptr;
-    void* p_cq = nullptr;
+    alloc_rings();
     void* p_stop = nullptr;
-    HIP_CHECK(hipHostMalloc(&p_tail, 8, hipHostMallocMapped));
-    HIP_CHECK(hipHostMalloc(&p_cq, kRing * 8, hipHostMallocMapped));
     HIP_CHECK(hipHostMalloc(&p_stop, 4, hipHostMallocMapped));
-    sq_tail_ = static_cast<volatile unsigned long long*>(p_tail);
-    cq_ = static_cast<volatile unsigned long long*>(p_cq);
     stop_ = static_cast<volatile uint32_t*>(p_stop);
-    *sq_tail_ = 0;
     *stop_ = 0;
-    memset(const_cast<unsigned long long*>(cq_), 0, kRing * 8);
     // Device words: [0]=claim counter, [1]=known_tail, [2]=exit_flag.
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&claim_ctr_), 24));
     HIP_CHECK(hipMemset(claim_ctr_, 0, 24));
     HIP_CHECK(hipStreamSynchronize(nullptr));  // memset before launch()
-    desc_io_.resize(kRing, nullptr);
     launch();
   }
 
@@ -1119,101 +1320,28 @@ class HbmPersistentChannel : public HbmChannelBase {
           "persistent-channel teardown timeout; leaking rings");
       return;
     }
-    (void)hipHostFree(sq_);
-    (void)hipHostFree(const_cast<unsigned long long*>(sq_tail_));
-    (void)hipHostFree(const_cast<unsigned long long*>(cq_));
+    free_rings();
     (void)hipHostFree(const_cast<uint32_t*>(stop_));
     (void)hipFree(claim_ctr_);
     (void)hipStreamDestroy(stream_);
-    // Unfired completion callbacks (wedge teardown only): delete, never
-    // call, so their captures are released without touching torn state.
-    std::set<IoState*> leftovers(desc_io_.begin(), desc_io_.end());
-    for (IoState* state : leftovers) delete state;
+    delete_unfired();
   }
 
-  struct IoState {
-    IoCompletion cb;
-    uint32_t remaining;
-    int status;
-  };
-
-  void enqueue(IoRequest req, int status) {
-    if (status != kIoOk) {
-      immediate_.emplace_back(std::move(req.on_complete), status);
-      return;
-    }
-    if (req.op == IoOp::kFlush) {
-      flushes_.push_back({tail_, std::move(req.on_complete)});
-      return;
-    }
-    pending_.push_back(std::move(req));
-    drain_pending();
-  }
-
-  int poll() {
-    int completed = 0;
-    // Swap out the immediate list before firing: a completion callback
-    // may resubmit, and a failed resubmission appends to immediate_
-    // again — mutating the vector mid-iteration.
-    if (!immediate_.empty()) {
-      auto batch = std::move(immediate_);
-      immediate_.clear();
-      for (auto& [cb, status] : batch) {
-        if (cb) cb(status);
-        ++completed;
-      }
-    }
-    // Retire the contiguous completed prefix of the CQ.
-    while (completed_ < tail_) {
-      unsigned long long seq = __atomic_load_n(
-          const_cast<const unsigned long long*>(&cq_[completed_ % kRing]),
-          __ATOMIC_ACQUIRE);
-      if (seq != completed_ + 1) break;
-      IoState* state = desc_io_[completed_ % kRing];
-      desc_io_[completed_ % kRing] = nullptr;
-      ++completed_;
-      if (state != nullptr && --state->remaining == 0) {
-        if (state->cb) state->cb(state->status);
-        delete state;
-        ++completed;
-      }
-    }
-    // Flush markers complete once their submission point is retired.
-    while (!flushes_.empty() && flushes_.front().first <= completed_) {
-      if (flushes_.front().second) flushes_.front().second(kIoOk);
-      flushes_.pop_front();
-      ++completed;
-    }
-    drain_pending();
-    if (completed > 0) last_progress_ = std::chrono::steady_clock::now();
-    // Liveness: if work is outstanding but nothing completed for a
-    // while, the service kernel may have idle-exited in the submit
-    // race window — relaunch from the completed prefix (descriptor
-    // replay is idempotent). The 1 ms stall gate keeps hipStreamQuery
-    // (a locked runtime call) out of the hot path: unthrottled, 8
-    // polling threads serialized on it and collapsed throughput.
-    if (completed_ < tail_) {
-      const auto now = std::chrono::steady_clock::now();
-      if (now - last_progress_ > std::chrono::milliseconds(1)) {
-        g_pers_stall_queries.fetch_add(1, std::memory_order_relaxed);
-        if (hipStreamQuery(stream_) == hipSuccess) {
-          g_pers_relaunches.fetch_add(1, std::memory_order_relaxed);
-          launch();
-        }
-        debug_dump_state();
-        last_progress_ = now;  // gate the query itself to 1/ms
-      }
-    }
-    return completed;
-  }
-
-  bool has_capacity(uint32_t tiles) const {
-    return tail_ - completed_ + tiles <= kRing;
-  }
-
-  uint8_t* base() { return base_; }
+  const char* kind_name() const override { return "persistent"; }
 
  private:
+  // The service kernel may have idle-exited in the submit race window:
+  // relaunch it if its stream is empty. Runs at most once per ms (the
+  // base's stall gate), which keeps hipStreamQuery off the hot path.
+  void on_stall() override {
+    g_pers_stall_queries.fetch_add(1, std::memory_order_relaxed);
+    if (hipStreamQuery(stream_) == hipSuccess) {
+      g_pers_relaunches.fetch_add(1, std::memory_order_relaxed);
+      launch();
+    }
+    debug_dump_state();
+  }
+
   void launch() {
     g_pers_launches.fetch_add(1, std::memory_order_relaxed);
     (void)hipSetDevice(device_);
@@ -1255,53 +1383,6 @@ class HbmPersistentChannel : public HbmChannelBase {
     last_progress_ = std::chrono::steady_clock::now();
   }
 
-  void drain_pending() {
-    while (!pending_.empty()) {
-      IoRequest& req = pending_.front();
-      const uint32_t tiles = static_cast<uint32_t>(
-          (req.length + kTileBytes - 1) / kTileBytes);
-      if (!has_capacity(tiles)) return;
-      auto* state = new IoState{std::move(req.on_complete), tiles, kIoOk};
-      uint64_t done = 0;
-      uint64_t t = tail_;
-      while (done < req.length) {
-        const uint32_t bytes = static_cast<uint32_t>(
-            std::min<uint64_t>(kTileBytes, req.length - done));
-        BlockDesc& d = sq_[t % kRing];
-        if (req.op == IoOp::kRead) {
-          d.src = base_ + req.offset + done;
-          d.dst = buf_device(static_cast<uint8_t*>(req.buffer) + done);
-        } else if (req.op == IoOp::kWrite) {
-          d.src = buf_device(static_cast<uint8_t*>(req.buffer) + done);
-          d.dst = base_ + req.offset + done;
-        } else {
-          d.src = nullptr;
-          d.dst = base_ + req.offset + done;
-        }
-        d.bytes = bytes;
-        d.fill = req.fill;
-        desc_io_[t % kRing] = state;
-        ++t;
-        done += bytes;
-      }
-      tail_ = t;
-      // Publish: descriptors before the tail, release order.
-      __atomic_store_n(const_cast<unsigned long long*>(sq_tail_), tail_,
-                       __ATOMIC_RELEASE);
-      pending_.pop_front();
-    }
-  }
-
-  uint8_t* buf_device(uint8_t* host) {
-    void* dev = nullptr;
-    hipError_t err = hipHostGetDevicePointer(&dev, host, 0);
-    if (err != hipSuccess) {
-      throw std::runtime_error(
-          "hipstore: I/O buffer is not pinned host memory (use alloc_pinned)");
-    }
-    return static_cast<uint8_t*>(dev);
-  }
-
   // HIPSTORE_DEBUG: once a second during a stall, read the device
   // control words back on a utility stream and print them — shows
   // whether the leader mirrored the tail and how far workers claimed.
@@ -1333,21 +1414,10 @@ class HbmPersistentChannel : public HbmChannelBase {
   std::chrono::steady_clock::time_point dbg_last_{};
   hipStream_t dbg_stream_ = nullptr;
 
-  uint8_t* base_;
   int device_;
   hipStream_t stream_ = nullptr;
-  BlockDesc* sq_ = nullptr;
-  volatile unsigned long long* sq_tail_ = nullptr;
-  volatile unsigned long long* cq_ = nullptr;
   volatile uint32_t* stop_ = nullptr;
   unsigned long long* claim_ctr_ = nullptr;
-  std::chrono::steady_clock::time_point last_progress_;
-  uint64_t tail_ = 0;
-  uint64_t completed_ = 0;
-  std::vector<IoState*> desc_io_;
-  std::deque<IoRequest> pending_;
-  std::deque<std::pair<uint64_t, IoCompletion>> flushes_;
-  std::vector<std::pair<IoCompletion, int>> immediate_;
 };
 
 // Host side of the shared service kernel: one per device, multiplexing
@@ -1540,29 +1610,14 @@ class SharedService {
 };
 
 // Channel whose ring is serviced by the per-device shared kernel.
-// Ring/completion bookkeeping mirrors HbmPersistentChannel; the
-// difference is who runs the GPU side.
-class HbmSharedChannel : public HbmChannelBase {
+class HbmSharedChannel : public ServiceRingChannel {
  public:
-  static constexpr uint32_t kRing = 32768;
-
-  HbmSharedChannel(int device, uint8_t* base)
-      : HbmChannelBase(Kind::kShared), base_(base) {
+  HbmSharedChannel(int device, uint8_t* base) : ServiceRingChannel(base) {
     SharedService::dbg("chan:instance");
     service_ = SharedService::instance(device);
     SharedService::dbg("chan:hostmalloc");
     HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sq_),
-                            kRing * sizeof(BlockDesc), hipHostMallocMapped));
-    void* p_tail = nullptr;
-    void* p_cq = nullptr;
-    HIP_CHECK(hipHostMalloc(&p_tail, 8, hipHostMallocMapped));
-    HIP_CHECK(hipHostMalloc(&p_cq, kRing * 8, hipHostMallocMapped));
-    sq_tail_ = static_cast<volatile unsigned long long*>(p_tail);
-    cq_ = static_cast<volatile unsigned long long*>(p_cq);
-    *sq_tail_ = 0;
-    memset(const_cast<unsigned long long*>(cq_), 0, kRing * 8);
-    desc_io_.resize(kRing, nullptr);
+    alloc_rings();
     SharedService::dbg("chan:attach");
     slot_ = service_->attach(
         device_view(sq_), device_view(const_cast<unsigned long long*>(sq_tail_)),
@@ -1578,41 +1633,19 @@ class HbmSharedChannel : public HbmChannelBase {
       poll();
     }
     service_->detach(slot_);
-    std::set<IoState*> leftovers(desc_io_.begin(), desc_io_.end());
-    for (IoState* state : leftovers) {
-      if (state != nullptr) delete state;  // undrained multi-tile IOs
-    }
+    delete_unfired();
     if (completed_ < tail_) {
       // The drain timed out: a wedged service worker may still hold a
       // claim into these rings — leak them rather than fault the GPU.
       dump_engine_stats("shared-channel teardown timeout; leaking rings");
       return;
     }
-    (void)hipHostFree(sq_);
-    (void)hipHostFree(const_cast<unsigned long long*>(sq_tail_));
-    (void)hipHostFree(const_cast<unsigned long long*>(cq_));
+    free_rings();
   }
 
-  struct IoState {
-    IoCompletion cb;
-    uint32_t remaining;
-    int status;
-  };
+  const char* kind_name() const override { return "shared"; }
 
-  void enqueue(IoRequest req, int status) {
-    if (status != kIoOk) {
-      immediate_.emplace_back(std::move(req.on_complete), status);
-      return;
-    }
-    if (req.op == IoOp::kFlush) {
-      flushes_.push_back({tail_, std::move(req.on_complete)});
-      return;
-    }
-    pending_.push_back(std::move(req));
-    drain_pending();
-  }
-
-  int poll() {
+  int poll() override {
     static const bool debug_env = getenv("HIPSTORE_DEBUG") != nullptr;
     if (debug_env) {
       const auto now = std::chrono::steady_clock::now();
@@ -1628,116 +1661,20 @@ class HbmSharedChannel : public HbmChannelBase {
                 st[0], st[1], st[2]);
       }
     }
-    int completed = 0;
-    // Swap out the immediate list before firing: a completion callback
-    // may resubmit, and a failed resubmission appends to immediate_
-    // again — mutating the vector mid-iteration.
-    if (!immediate_.empty()) {
-      auto batch = std::move(immediate_);
-      immediate_.clear();
-      for (auto& [cb, status] : batch) {
-        if (cb) cb(status);
-        ++completed;
-      }
-    }
-    while (completed_ < tail_) {
-      unsigned long long seq = __atomic_load_n(
-          const_cast<const unsigned long long*>(&cq_[completed_ % kRing]),
-          __ATOMIC_ACQUIRE);
-      if (seq != completed_ + 1) break;
-      IoState* state = desc_io_[completed_ % kRing];
-      desc_io_[completed_ % kRing] = nullptr;
-      ++completed_;
-      if (state != nullptr && --state->remaining == 0) {
-        if (state->cb) state->cb(state->status);
-        delete state;
-        ++completed;
-      }
-    }
-    if (completed > 0) {
-      service_->update_prefix(slot_, completed_);
-      last_progress_ = std::chrono::steady_clock::now();
-    }
-    while (!flushes_.empty() && flushes_.front().first <= completed_) {
-      if (flushes_.front().second) flushes_.front().second(kIoOk);
-      flushes_.pop_front();
-      ++completed;
-    }
-    drain_pending();
-    if (completed_ < tail_ &&
-        std::chrono::steady_clock::now() - last_progress_ >
-            std::chrono::milliseconds(1)) {
-      service_->ensure_running();
-      last_progress_ = std::chrono::steady_clock::now();
-    }
-    return completed;
-  }
-
-  bool has_capacity(uint32_t tiles) const {
-    return tail_ - completed_ + tiles <= kRing;
+    return ServiceRingChannel::poll();
   }
 
  private:
-  void drain_pending() {
-    while (!pending_.empty()) {
-      IoRequest& req = pending_.front();
-      const uint32_t tiles = static_cast<uint32_t>(
-          (req.length + kTileBytes - 1) / kTileBytes);
-      if (!has_capacity(tiles)) return;
-      auto* state = new IoState{std::move(req.on_complete), tiles, kIoOk};
-      uint64_t done = 0;
-      uint64_t t = tail_;
-      while (done < req.length) {
-        const uint32_t bytes = static_cast<uint32_t>(
-            std::min<uint64_t>(kTileBytes, req.length - done));
-        BlockDesc& d = sq_[t % kRing];
-        if (req.op == IoOp::kRead) {
-          d.src = base_ + req.offset + done;
-          d.dst = buf_device(static_cast<uint8_t*>(req.buffer) + done);
-        } else if (req.op == IoOp::kWrite) {
-          d.src = buf_device(static_cast<uint8_t*>(req.buffer) + done);
-          d.dst = base_ + req.offset + done;
-        } else {
-          d.src = nullptr;
-          d.dst = base_ + req.offset + done;
-        }
-        d.bytes = bytes;
-        d.fill = req.fill;
-        desc_io_[t % kRing] = state;
-        ++t;
-        done += bytes;
-      }
-      tail_ = t;
-      __atomic_store_n(const_cast<unsigned long long*>(sq_tail_), tail_,
-                       __ATOMIC_RELEASE);
-      pending_.pop_front();
-    }
+  // A relaunch of the service restarts this ring's claims from here.
+  void on_retired(uint64_t completed) override {
+    service_->update_prefix(slot_, completed);
   }
 
-  uint8_t* buf_device(uint8_t* host) {
-    void* dev = nullptr;
-    hipError_t err = hipHostGetDevicePointer(&dev, host, 0);
-    if (err != hipSuccess) {
-      throw std::runtime_error(
-          "hipstore: I/O buffer is not pinned host memory (use alloc_pinned)");
-    }
-    return static_cast<uint8_t*>(dev);
-  }
+  void on_stall() override { service_->ensure_running(); }
 
-  uint8_t* base_;
   std::shared_ptr<SharedService> service_;
   std::chrono::steady_clock::time_point dbg_last_{};
   int slot_ = -1;
-  BlockDesc* sq_ = nullptr;
-  volatile unsigned long long* sq_tail_ = nullptr;
-  volatile unsigned long long* cq_ = nullptr;
-  uint64_t tail_ = 0;
-  uint64_t completed_ = 0;
-  std::vector<IoState*> desc_io_;
-  std::deque<IoRequest> pending_;
-  std::deque<std::pair<uint64_t, IoCompletion>> flushes_;
-  std::vector<std::pair<IoCompletion, int>> immediate_;
-  std::chrono::steady_clock::time_point last_progress_{};
 };
 
 class HbmBdev : public Bdev {
@@ -1871,51 +1808,11 @@ class HbmBdev : public Bdev {
       }
     }
     if (status == kIoOk) account(req);
-    auto* channel = static_cast<HbmChannelBase*>(ch);
-    switch (channel->kind) {
-      case HbmChannelBase::Kind::kShared:
-        static_cast<HbmSharedChannel*>(channel)->enqueue(std::move(req), status);
-        break;
-      case HbmChannelBase::Kind::kPersistent:
-        static_cast<HbmPersistentChannel*>(channel)->enqueue(std::move(req),
-                                                             status);
-        break;
-      case HbmChannelBase::Kind::kBatched:
-        static_cast<HbmChannel*>(channel)->enqueue(std::move(req), status);
-        break;
-    }
+    hbm_channel(ch)->enqueue(std::move(req), status);
   }
 
   int poll(IoChannel* ch) override {
-    // Dispatch on the CHANNEL's kind, exactly like submit(): a
-    // persistent bdev hands out batched/shared channels past the
-    // per-queue cap, and polling those through bdev-level flags cast
-    // them to the wrong class (round-1's "mixed-engine wedge": the
-    // misdispatched poll read garbage — stalled batched fallbacks,
-    // segfaulted shared ones — while the GPU side was healthy all
-    // along). No HIP API calls on the persistent paths: poll() runs
-    // in a tight loop on every submitter thread, and even
-    // hipSetDevice takes the runtime's global lock — 4+ spinning
-    // threads convoyed on it and starved each other.
-    auto* channel = static_cast<HbmChannelBase*>(ch);
-    switch (channel->kind) {
-      case HbmChannelBase::Kind::kShared:
-        return static_cast<HbmSharedChannel*>(channel)->poll();
-      case HbmChannelBase::Kind::kPersistent:
-        return static_cast<HbmPersistentChannel*>(channel)->poll();
-      case HbmChannelBase::Kind::kBatched:
-        break;
-    }
-    auto* batched = static_cast<HbmChannel*>(channel);
-    int completed = batched->retire(/*wait=*/false);
-    if (batched->has_pending()) {
-      // Launches must come from the bdev's device; only pay the
-      // runtime call when there is something to launch.
-      (void)hipSetDevice(device_);
-      batched->kick();
-      completed += batched->retire(/*wait=*/false);
-    }
-    return completed;
+    return hbm_channel(ch)->poll();
   }
 
  private:
@@ -2464,15 +2361,9 @@ IoQueue::IoQueue(BdevPtr bdev)
 
 const char* IoQueue::kind() const {
   // Only HbmBdev exposes a device base, and every channel it hands out
-  // derives from HbmChannelBase, whose tag is the single source of
-  // truth for the engine serving this queue.
+  // derives from HbmChannelBase, which names the engine serving it.
   if (bdev_->device_base() == nullptr) return "cpu";
-  switch (static_cast<HbmChannelBase*>(channel_.get())->kind) {
-    case HbmChannelBase::Kind::kBatched: return "batched";
-    case HbmChannelBase::Kind::kPersistent: return "persistent";
-    case HbmChannelBase::Kind::kShared: return "shared";
-  }
-  return "unknown";
+  return hbm_channel(channel_.get())->kind_name();
 }
 
 std::vector<IoQueue::Result> IoQueue::run(const std::vector<Op>& ops) {
@@ -2662,22 +2553,134 @@ void maybe_pin_thread(int queue_index) {
   (void)pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
 }
 
+struct PerfQueueStats {
+  uint64_t ios = 0;
+  LatHist lat;
+};
+
+// One benchmark queue, shared by run_bdevperf and PerfSession:
+// queue_depth buffer slots on one channel, each slot resubmitting a
+// fresh random request from its completion callback while `limit`
+// allows. The callers own the channel and the poll loop: they decide
+// when to stop submitting (by lowering `limit`) and what an error or a
+// stall means for their run.
+class PerfQueue {
+ public:
+  using clock = std::chrono::steady_clock;
+
+  // `on_error` runs in the completion callback of every failed I/O.
+  PerfQueue(Bdev* bdev, IoChannel* channel, const std::string& workload,
+            uint32_t io_size, uint32_t queue_depth, int q,
+            PerfQueueStats* stats, std::function<void(PerfQueue&)> on_error)
+      : bdev_(bdev),
+        channel_(channel),
+        do_read_(workload != "randwrite"),
+        do_write_(workload == "randwrite" || workload == "randrw"),
+        io_size_(io_size),
+        queue_depth_(queue_depth),
+        units_(bdev->size_bytes() / io_size),
+        rng_(0x9E3779B97F4A7C15ULL ^ (q * 0x8DA6B343)),
+        submit_ts_(queue_depth),
+        stats_(stats),
+        on_error_(std::move(on_error)) {
+    const size_t bytes = static_cast<size_t>(io_size) * queue_depth;
+    buf_ = static_cast<uint8_t*>(alloc_pinned(bytes));
+    // Writes carry a defined pattern, not whatever the allocator
+    // handed back (zero pages or stale heap contents).
+    if (do_write_) memset(buf_, 0x5A, bytes);
+  }
+
+  // Call once nothing is in flight. After a stall (or an exception)
+  // the buffer is leaked instead: outstanding descriptors reference it.
+  void free_buffer() { free_pinned(buf_); }
+
+  // Begin a run of at most `new_limit` I/Os: fill the queue.
+  void start(uint64_t new_limit) {
+    limit = new_limit;
+    submitted = 0;
+    const uint32_t initial =
+        static_cast<uint32_t>(std::min<uint64_t>(queue_depth_, limit));
+    for (uint32_t slot = 0; slot < initial; ++slot) submit(slot);
+    last_progress_ = clock::now();
+    empty_polls_ = 0;
+  }
+
+  // One poll of the channel. Returns false when the stall watchdog
+  // fires: in-flight I/Os stopped completing for the sync-timeout
+  // window (checked only on empty polls, every 1024th), so a wedged
+  // engine costs the caller seconds instead of a thread spinning
+  // forever.
+  bool poll() {
+    if (bdev_->poll(channel_) == 0) {
+      __builtin_ia32_pause();  // spinning submitter hygiene
+      if ((++empty_polls_ & 0x3FF) == 0 && inflight > 0 &&
+          clock::now() - last_progress_ >
+              std::chrono::duration<double>(sync_io_timeout_s())) {
+        return false;
+      }
+    } else {
+      last_progress_ = clock::now();
+      empty_polls_ = 0;
+    }
+    return true;
+  }
+
+  uint64_t limit = 0;      // a slot resubmits while submitted < limit
+  uint64_t submitted = 0;  // since start()
+  uint32_t inflight = 0;
+
+ private:
+  void submit(uint32_t slot) {
+    IoRequest req;
+    const bool write = do_write_ && (!do_read_ || (rng_() & 1));
+    req.op = write ? IoOp::kWrite : IoOp::kRead;
+    req.offset = (rng_() % units_) * io_size_;
+    req.length = io_size_;
+    req.buffer = buf_ + static_cast<size_t>(slot) * io_size_;
+    submit_ts_[slot] = clock::now();
+    req.on_complete = [this, slot](int status) { complete(slot, status); };
+    ++inflight;
+    ++submitted;
+    bdev_->submit(channel_, std::move(req));
+  }
+
+  void complete(uint32_t slot, int status) {
+    if (status != kIoOk) on_error_(*this);
+    stats_->lat.record(static_cast<uint32_t>(std::min<int64_t>(
+        std::chrono::duration_cast<std::chrono::microseconds>(
+            clock::now() - submit_ts_[slot]).count(), UINT32_MAX)));
+    ++stats_->ios;
+    --inflight;
+    if (submitted < limit) submit(slot);
+  }
+
+  Bdev* bdev_;
+  IoChannel* channel_;
+  const bool do_read_;
+  const bool do_write_;
+  const uint32_t io_size_;
+  const uint32_t queue_depth_;
+  const uint64_t units_;
+  std::mt19937_64 rng_;
+  std::vector<clock::time_point> submit_ts_;
+  PerfQueueStats* stats_;
+  std::function<void(PerfQueue&)> on_error_;
+  uint8_t* buf_ = nullptr;
+  clock::time_point last_progress_{};
+  uint32_t empty_polls_ = 0;
+};
+
 }  // namespace
 
 PerfResult run_bdevperf(Bdev* bdev, const std::string& workload,
                         uint32_t io_size, uint32_t queue_depth,
                         int num_queues, double seconds, uint64_t max_ios) {
   using clock = std::chrono::steady_clock;
-  const bool do_read = workload != "randwrite";
-  const bool do_write = workload == "randwrite" || workload == "randrw";
-  const uint64_t units = bdev->size_bytes() / io_size;
-  if (units == 0) throw std::runtime_error("bdev smaller than io_size");
+  if (bdev->size_bytes() / io_size == 0) {
+    throw std::runtime_error("bdev smaller than io_size");
+  }
 
-  struct QueueStats {
-    uint64_t ios = 0;
-    LatHist lat;
-  };
-  std::vector<QueueStats> stats(num_queues);
+  std::vector<PerfQueueStats> stats(num_queues);
   std::vector<std::thread> threads;
   std::atomic<bool> failed{false};
   const auto t0 = clock::now();
@@ -2692,94 +2695,36 @@ PerfResult run_bdevperf(Bdev* bdev, const std::string& workload,
         maybe_pin_thread(q);
         auto channel = bdev->get_channel();
         if (dbg) fprintf(stderr, "[hipstore-dbg] q%d got-channel\n", q);
-        uint8_t* buf = static_cast<uint8_t*>(
-            alloc_pinned(static_cast<size_t>(io_size) * queue_depth));
+        // Abort the run on the first error (SPDK bdevperf semantics):
+        // drain and stop rather than hammering a dead/failing bdev for
+        // the rest of the duration.
+        PerfQueue queue(bdev, channel.get(), workload, io_size, queue_depth,
+                        q, &stats[q], [&failed](PerfQueue& failing) {
+                          failed.store(true);
+                          failing.limit = 0;
+                        });
         if (dbg) fprintf(stderr, "[hipstore-dbg] q%d pinned-buf\n", q);
-        // Writes carry a defined pattern, not whatever the allocator
-        // handed back (zero pages or stale heap contents).
-        if (do_write) {
-          memset(buf, 0x5A, static_cast<size_t>(io_size) * queue_depth);
-        }
-        std::mt19937_64 rng(0x9E3779B97F4A7C15ULL ^ (q * 0x8DA6B343));
-        QueueStats& st = stats[q];
-        std::vector<clock::time_point> submit_ts(queue_depth);
-        uint32_t inflight = 0;
-        bool stopping = false;
-        uint64_t submitted = 0;
-
-        std::function<void(uint32_t)> submit_slot = [&](uint32_t slot) {
-          IoRequest req;
-          bool write = do_write && (!do_read || (rng() & 1));
-          req.op = write ? IoOp::kWrite : IoOp::kRead;
-          req.offset = (rng() % units) * io_size;
-          req.length = io_size;
-          req.buffer = buf + static_cast<size_t>(slot) * io_size;
-          submit_ts[slot] = clock::now();
-          req.on_complete = [&, slot](int status) {
-            if (status != kIoOk) {
-              // Abort the run on the first error (SPDK bdevperf
-              // semantics): drain and stop rather than hammering a
-              // dead/failing bdev for the rest of the duration.
-              failed.store(true);
-              stopping = true;
-            }
-            const auto now = clock::now();
-            st.lat.record(static_cast<uint32_t>(std::min<int64_t>(
-                std::chrono::duration_cast<std::chrono::microseconds>(
-                    now - submit_ts[slot]).count(), UINT32_MAX)));
-            ++st.ios;
-            --inflight;
-            if (!stopping) {
-              submit_slot(slot);
-              ++inflight;
-              ++submitted;
-            }
-          };
-          bdev->submit(channel.get(), std::move(req));
-        };
-
-        for (uint32_t slot = 0; slot < queue_depth; ++slot) {
-          submit_slot(slot);
-          ++inflight;
-          ++submitted;
-        }
+        queue.start(UINT64_MAX);
         if (dbg) fprintf(stderr, "[hipstore-dbg] q%d submitted-initial\n", q);
-        // Stall watchdog: if in-flight I/Os stop completing for the
-        // sync-timeout window, abandon the queue (failed) instead of
-        // spinning forever — checked only on empty polls, every 1024th.
-        auto last_progress = clock::now();
-        uint32_t empty_polls = 0;
-        bool stalled = false;
-        while (true) {
-          if (bdev->poll(channel.get()) == 0) {
-            __builtin_ia32_pause();  // spinning submitter hygiene
-            if ((++empty_polls & 0x3FF) == 0 && inflight > 0 &&
-                clock::now() - last_progress >
-                    std::chrono::duration<double>(sync_io_timeout_s())) {
-              stalled = true;
-              break;
-            }
-          } else {
-            last_progress = clock::now();
-            empty_polls = 0;
+        // Keep the queue full until the deadline, the I/O cap or a
+        // failure on any queue; then let it drain.
+        while (queue.limit != 0 || queue.inflight > 0) {
+          if (!queue.poll()) {
+            fprintf(stderr,
+                    "[hipstore] bdevperf q%d stalled (%u in flight); "
+                    "abandoning queue\n", q, queue.inflight);
+            dump_engine_stats("bdevperf stall");
+            failed.store(true);
+            return;  // buffer leaked, see PerfQueue::free_buffer
           }
-          if (!stopping &&
+          if (queue.limit != 0 &&
               (failed.load(std::memory_order_relaxed) ||
                clock::now() >= deadline ||
-               (per_queue_cap && submitted >= per_queue_cap))) {
-            stopping = true;
+               (per_queue_cap && queue.submitted >= per_queue_cap))) {
+            queue.limit = 0;
           }
-          if (stopping && inflight == 0) break;
         }
-        if (stalled) {
-          fprintf(stderr,
-                  "[hipstore] bdevperf q%d stalled (%u in flight); "
-                  "abandoning queue\n", q, inflight);
-          dump_engine_stats("bdevperf stall");
-          failed.store(true);
-          return;  // leak buf: outstanding descriptors reference it
-        }
-        free_pinned(buf);
+        queue.free_buffer();
       } catch (const std::exception&) {
         failed.store(true);
       }
@@ -2840,28 +2785,21 @@ struct PerfSession::Impl {
   uint64_t per_queue_ios = 0;   // target for the current epoch
   bool stop = false;
 
-  struct QueueStats {
+  struct QueueStats : PerfQueueStats {
     uint64_t done_epoch = 0;
-    uint64_t ios = 0;
-    LatHist lat;
     bool failed = false;
   };
   std::vector<QueueStats> stats;
   std::vector<std::thread> threads;
 
   void worker(int q) {
-    using clock = std::chrono::steady_clock;
     try {
       maybe_pin_thread(q);
       auto channel = bdev->get_channel();
-      uint8_t* buf = static_cast<uint8_t*>(
-          alloc_pinned(static_cast<size_t>(io_size) * queue_depth));
-      std::mt19937_64 rng(0x9E3779B97F4A7C15ULL ^ (q * 0x8DA6B343));
-      const uint64_t units = bdev->size_bytes() / io_size;
-      const bool do_read = workload != "randwrite";
-      const bool do_write = workload == "randwrite" || workload == "randrw";
-      std::vector<clock::time_point> submit_ts(queue_depth);
       QueueStats& st = stats[q];
+      PerfQueue queue(bdev.get(), channel.get(), workload, io_size,
+                      queue_depth, q, &st,
+                      [&st](PerfQueue&) { st.failed = true; });
 
       uint64_t my_epoch = 0;
       while (true) {
@@ -2871,81 +2809,30 @@ struct PerfSession::Impl {
           if (stop) break;
           my_epoch = epoch;
         }
-        const uint64_t target = per_queue_ios;
-        uint64_t completed = 0, submitted = 0;
-        uint32_t inflight = 0;
+        st.ios = 0;
         st.lat.reset();
-
-        std::function<void(uint32_t)> submit_slot = [&](uint32_t slot) {
-          IoRequest req;
-          bool write = do_write && (!do_read || (rng() & 1));
-          req.op = write ? IoOp::kWrite : IoOp::kRead;
-          req.offset = (rng() % units) * io_size;
-          req.length = io_size;
-          req.buffer = buf + static_cast<size_t>(slot) * io_size;
-          submit_ts[slot] = clock::now();
-          req.on_complete = [&, slot](int status) {
-            if (status != kIoOk) st.failed = true;
-            st.lat.record(static_cast<uint32_t>(std::min<int64_t>(
-                std::chrono::duration_cast<std::chrono::microseconds>(
-                    clock::now() - submit_ts[slot]).count(), UINT32_MAX)));
-            ++completed;
-            --inflight;
-            if (submitted < target) {
-              submit_slot(slot);
-              ++inflight;
-              ++submitted;
-            }
-          };
-          bdev->submit(channel.get(), std::move(req));
-        };
-
-        const uint32_t initial =
-            static_cast<uint32_t>(std::min<uint64_t>(queue_depth, target));
-        for (uint32_t slot = 0; slot < initial; ++slot) {
-          submit_slot(slot);
-          ++inflight;
-          ++submitted;
-        }
-        // Stall watchdog (checked on every 1024th empty poll): a
-        // wedged engine fails the step in seconds instead of pinning
-        // this thread — and step()'s cv.wait — forever.
-        auto last_progress = clock::now();
-        uint32_t empty_polls = 0;
-        bool stalled = false;
-        while (inflight > 0) {
-          if (bdev->poll(channel.get()) == 0) {
-            __builtin_ia32_pause();
-            if ((++empty_polls & 0x3FF) == 0 &&
-                clock::now() - last_progress >
-                    std::chrono::duration<double>(sync_io_timeout_s())) {
-              stalled = true;
-              break;
-            }
-          } else {
-            last_progress = clock::now();
-            empty_polls = 0;
+        // Exactly the step's per-queue target, then drain.
+        queue.start(per_queue_ios);
+        while (queue.inflight > 0) {
+          if (!queue.poll()) {
+            fprintf(stderr,
+                    "[hipstore] perf-session q%d stalled (%u in flight); "
+                    "failing the session\n", q, queue.inflight);
+            dump_engine_stats("perf-session stall");
+            std::lock_guard<std::mutex> lock(mutex);
+            st.failed = true;
+            st.done_epoch = ~0ull;  // never blocks step()
+            cv.notify_all();
+            return;  // buffer leaked, see PerfQueue::free_buffer
           }
         }
-        if (stalled) {
-          fprintf(stderr,
-                  "[hipstore] perf-session q%d stalled (%u in flight); "
-                  "failing the session\n", q, inflight);
-          dump_engine_stats("perf-session stall");
-          std::lock_guard<std::mutex> lock(mutex);
-          st.failed = true;
-          st.done_epoch = ~0ull;  // never blocks step()
-          cv.notify_all();
-          return;  // leak buf: outstanding descriptors reference it
-        }
-        st.ios = completed;
         {
           std::lock_guard<std::mutex> lock(mutex);
           st.done_epoch = my_epoch;
         }
         cv.notify_all();
       }
-      free_pinned(buf);
+      queue.free_buffer();
     } catch (const std::exception&) {
       std::lock_guard<std::mutex> lock(mutex);
       stats[q].failed = true;

@@ -123,6 +123,18 @@ class TestPerfEdgeCases:
         r = s.step(1000)
         assert r["io_count"] >= 1000
 
+    def test_session_step_counts(self):
+        """CPU variant of test_engine_matrix's
+        test_perf_session_step_counts: every count follows from
+        per_queue_ios = ceil(total / num_queues) with two queues of
+        depth 4."""
+        b = hs.create_malloc_bdev(f"edge3-{random.random()}", 512, 16384)
+        assert hs.IoQueue(b).kind == "cpu"
+        s = hs.PerfSession(b, "randrw", 4096, 4, 2)
+        assert s.step(10)["io_count"] == 10  # 2 x 5: resubmits from callbacks
+        assert s.step(3)["io_count"] == 4    # 2 x 2: below the queue depth
+        assert s.step(10)["io_count"] == 10
+
     def test_bdevperf_max_ios_cap(self):
         b = hs.create_malloc_bdev(f"edge2-{random.random()}", 512, 8192)
         r = hs.run_bdevperf(b, "randread", 4096, 8, 2, 60.0, max_ios=500)

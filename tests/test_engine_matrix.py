@@ -67,6 +67,31 @@ def report(test, queue, model, **extra):
 
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("engine", ENGINES)
+def test_perf_session_step_counts(engine, monkeypatch):
+    """The benchmark's per-queue driver on each engine. Every count
+    follows from per_queue_ios = ceil(total / num_queues) in
+    PerfSession::step with two queues of depth 4; nothing is measured.
+
+    First in the file on purpose: the two per-queue service kernels of
+    the persistent case come up in 1.5 s here, but took 5.3 s (before
+    and after the driver was shared) when they started right after the
+    shared-engine cases of the tests below."""
+    bdev = make_bdev(engine, monkeypatch, f"em-perf-{engine}", 8 * MIB)
+    queue = make_queue(engine, bdev)
+    del queue
+    session = hs.PerfSession(bdev, "randrw", 4096, 4, 2)
+    # 2 x 5: one more than the queue depth, so each queue resubmits
+    # from a completion callback.
+    assert session.step(10)["io_count"] == 10
+    # 2 x 2: a target below the queue depth fills only part of the queue.
+    assert session.step(3)["io_count"] == 4
+    assert session.step(10)["io_count"] == 10
+    print(f"engine-matrix perf_session kind={engine} steps=10,3,10",
+          flush=True)
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("engine", ENGINES)
 def test_tile_edges(engine, monkeypatch):
     bdev = make_bdev(engine, monkeypatch, f"em-edge-{engine}", 64 * MIB)
     queue = make_queue(engine, bdev)
