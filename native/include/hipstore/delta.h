@@ -1,0 +1,76 @@
+// Incremental checkpoints of bdevs to files ("hipstore delta file,
+// version 1"): the third persistence escape next to save_config
+// (topology only) and AIO bdevs (never in HBM). A file holds the marked
+// granules of a volume as one dense stream (bdev_pack_marked_sync), so
+// an HBM volume leaves the GPU in one launch per staging window.
+//
+// Layout, little-endian, fully determined by the content:
+//   header, 64 bytes:
+//     "HSDELTA1", u32 version = 1, u32 block_size, u32 granule,
+//     u32 flags (bit 0 = full: no base, every granule present),
+//     u64 volume_bytes, u64 n_granules, u64 n_marked, u32 bitmap_crc,
+//     u32 0, u32 0, u32 header_crc (CRC32C of bytes 0-59)
+//   bitmap: ceil(n_granules / 64) * 8 bytes, bdev_diff_sync layout,
+//     tail bits 0
+//   records, each the next min(remaining, max(1, 2^20 / granule)) marked
+//     granules: u32 count, u32 crc32c(payload), count * granule bytes
+//   trailer, 16 bytes: "HSDEND1\0", u64 n_marked
+// All CRCs are crc32c_sw(0, ...).
+
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "hipstore/bdev.h"
+
+namespace hipstore {
+
+constexpr uint32_t kDeltaVersion = 1;
+constexpr uint32_t kDeltaFlagFull = 1;
+constexpr uint64_t kDeltaHeaderBytes = 64;
+constexpr uint64_t kDeltaTrailerBytes = 16;
+constexpr uint64_t kDeltaRecordBytes = 1ull << 20;
+
+struct DeltaInfo {
+  uint32_t version = 0;
+  uint32_t block_size = 0;
+  uint32_t granule = 0;
+  bool full = false;
+  uint64_t volume_bytes = 0;
+  uint64_t n_granules = 0;
+  uint64_t n_marked = 0;  // granules in the file (saved / applied)
+  uint64_t file_bytes = 0;
+};
+
+// Every call returns an IoStatus and, on failure, a one-line reason in
+// `error`: kIoInvalid for bad parameters, mismatched geometry and
+// malformed or corrupt files; kIoFailed for I/O failures, a claimed
+// import target and an existing file without `overwrite`.
+
+// Writes the granules of `src` that differ from `base` (whole device,
+// bdev_diff_sync; equal block size and size required), or every granule
+// when `base` is null, to `path`. granule 0 = the block size. The file
+// appears under its final name only complete: it is written to
+// path + ".tmp", synced and renamed. Exporting a claimed volume is
+// allowed and advisory (crash-consistent at best).
+int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
+                      uint32_t granule, bool overwrite, DeltaInfo* stats,
+                      std::string* error);
+
+// Applies a delta file to `dst` from offset 0. A structural pass
+// (magic, version, both header CRCs, popcount, tail bits, exact file
+// length, trailer, block size, volume_bytes <= size of dst) runs before
+// the target is touched; records are then streamed through
+// bdev_unpack_marked_sync, each CRC checked before its bytes are handed
+// on. A bad record stops the import with the target partly updated.
+// dry_run runs every check and writes nothing. A claimed target is
+// refused.
+int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
+                      DeltaInfo* stats, std::string* error);
+
+// Header fields of a file after the structural pass.
+int delta_file_info(const std::string& path, DeltaInfo* info,
+                    std::string* error);
+
+}  // namespace hipstore

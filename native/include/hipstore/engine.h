@@ -10,6 +10,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -117,6 +118,66 @@ int bdev_copy_marked_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
                           uint32_t granule,
                           const std::vector<uint64_t>& bitmap,
                           uint64_t* copied = nullptr);
+
+// Gathers the granules of [src_offset, +length) whose bit is set in
+// `bitmap` (bdev_diff_sync layout) into one dense stream, in ascending
+// granule order, and hands it to `sink` in consecutive chunks:
+// sink(data, first_rank, count) receives marked granules number
+// first_rank .. first_rank + count - 1, `count * granule` bytes. A
+// non-zero return aborts the call with that status. Bits at or past the
+// last granule are ignored and not counted; no marked granule means no
+// launch and no callback.
+//
+// An HBM-resident bdev with a usable GPU runs hipstore::k_pack_marked on
+// its device, one launch per staging window, writing pinned host memory
+// in place; the callback for one window overlaps the kernel of the next.
+// Every other bdev reads runs of marked granules through bdev_read_sync
+// in spans of at most 1 MiB. Both paths cut the same chunks: every chunk
+// but the last holds max(1, staging_bytes / 2 / granule) granules
+// (staging_bytes 0 = two halves of 16 MiB).
+//
+// Validation is that of bdev_copy_marked_sync on the one bdev; also
+// kIoInvalid when the bitmap is shorter than the range or
+// 0 < staging_bytes < granule. `packed` receives the granules delivered.
+using PackSink =
+    std::function<int(const uint8_t* data, uint64_t first_rank, uint64_t count)>;
+int bdev_pack_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
+                          uint32_t granule,
+                          const std::vector<uint64_t>& bitmap,
+                          uint64_t staging_bytes, const PackSink& sink,
+                          uint64_t* packed = nullptr);
+
+// Inverse of bdev_pack_marked_sync: source(data, first_rank, count)
+// fills the next chunk of the dense stream (same chunking), which is
+// scattered to the marked granules of [dst_offset, +length)
+// (hipstore::k_unpack_marked on the GPU path, bdev_write_sync
+// otherwise). Unmarked granules of dst are never written. When `source`
+// fails, chunks delivered before it stay written. `unpacked` receives
+// the granules written.
+using UnpackSource =
+    std::function<int(uint8_t* data, uint64_t first_rank, uint64_t count)>;
+int bdev_unpack_marked_sync(Bdev* dst, uint64_t dst_offset, uint64_t length,
+                            uint32_t granule,
+                            const std::vector<uint64_t>& bitmap,
+                            uint64_t staging_bytes,
+                            const UnpackSource& source,
+                            uint64_t* unpacked = nullptr);
+
+// Measurement aid for tools/delta_bench.py: moves the marked bytes of
+// an HBM bdev to pinned host memory by plain hipMemcpyAsync (mode 0: one
+// copy of the same byte count, the PCIe ceiling; mode 1: one copy per
+// run of marked granules; both into a pinned ring of `ring_bytes`) or by
+// bdev_pack_marked_sync with `staging_bytes` and a sink that discards
+// (mode 2), and reports the host-clock time.
+struct MarkedCopyProbe {
+  double seconds = 0;
+  uint64_t granules = 0;  // marked granules moved
+  uint64_t calls = 0;     // hipMemcpyAsync calls / sink callbacks
+};
+int marked_copy_probe(Bdev* src, uint32_t granule,
+                      const std::vector<uint64_t>& bitmap, int mode,
+                      uint64_t ring_bytes, uint64_t staging_bytes,
+                      MarkedCopyProbe* out);
 
 // Synchronous convenience wrappers (tests, NBD pump): create a
 // throwaway channel, submit, poll to completion. Returns IoStatus.

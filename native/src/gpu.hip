@@ -247,6 +247,94 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_copy_marked(
   }
 }
 
+// --- marked gather / scatter (incremental checkpoints) ---------------------
+//
+// k_pack_marked moves the marked granules of one window [g_begin, g_end)
+// of a range into a dense buffer, in ascending granule order;
+// k_unpack_marked is its inverse. Same work split as k_copy_marked. A
+// granule's dense slot is a pure function of the bitmap:
+//   slot = rank_before_word[w] + popcount(word & ((1 << bit) - 1))
+//          - window_first_rank
+// rank_before_word is the exclusive prefix popcount of the bitmap,
+// built on the host next to the pinned bitmap copy (12 bytes of PCIe
+// reads per 64 granules), so there are no atomics, no ordering between
+// workgroups and nothing that depends on what the dense buffer held. A
+// window may begin and end inside a word: bits outside it are masked
+// for the walk but still counted below a bit, which is what subtracting
+// window_first_rank (marks before g_begin) expects. The host keeps
+// g_end <= n_granules, so stray tail bits of the caller's bitmap are
+// never visited, and they lie above every valid bit, so they are never
+// counted either. `window_count` bounds the slot: nothing outside
+// [0, window_count * granule) of the dense buffer is touched.
+struct MarkedWindow {
+  uint64_t g_begin;
+  uint64_t g_end;
+  uint32_t first_rank;  // marked granules before g_begin
+  uint32_t count;       // marked granules in the window
+};
+
+template <bool kPack>
+__device__ __forceinline__ void marked_window_walk(
+    uint8_t* __restrict__ bdev_base, uint8_t* __restrict__ dense,
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, const MarkedWindow win,
+    uint32_t granule_bytes) {
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule_bytes >> 4;
+  const uint64_t w_end = (win.g_end + 63) >> 6;
+  for (uint64_t w = (win.g_begin >> 6) + blockIdx.x; w < w_end;
+       w += gridDim.x) {
+    const unsigned long long word = bitmap[w];
+    const uint64_t g0 = w * 64;
+    unsigned long long inside = word;
+    if (g0 < win.g_begin) inside &= ~0ull << (win.g_begin - g0);
+    if (win.g_end - g0 < 64) inside &= (1ull << (win.g_end - g0)) - 1;
+    uint32_t bits = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(
+        (inside >> (wave * kDiffGranulesPerWave)) & 0xFFFFu));
+    if (bits == 0) continue;  // wave-uniform
+    const uint32_t rank0 =
+        __builtin_amdgcn_readfirstlane(rank_before_word[w]) - win.first_rank;
+    while (bits != 0) {
+      const uint32_t bit = wave * kDiffGranulesPerWave +
+                           static_cast<uint32_t>(__builtin_ctz(bits));
+      bits &= bits - 1;
+      const uint32_t slot =
+          rank0 + static_cast<uint32_t>(__popcll(word & ((1ull << bit) - 1)));
+      if (slot >= win.count) break;  // bitmap and ranks disagree: stay inside
+      uint4* __restrict__ pg = reinterpret_cast<uint4*>(
+          bdev_base + (g0 + bit) * granule_bytes);
+      uint4* __restrict__ ps = reinterpret_cast<uint4*>(
+          dense + static_cast<uint64_t>(slot) * granule_bytes);
+      if (kPack) {
+#pragma unroll 4
+        for (uint32_t i = lane; i < n16; i += 64) ps[i] = pg[i];
+      } else {
+#pragma unroll 4
+        for (uint32_t i = lane; i < n16; i += 64) pg[i] = ps[i];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_pack_marked(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dense,
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule_bytes) {
+  marked_window_walk<true>(const_cast<uint8_t*>(src), dense, bitmap,
+                           rank_before_word, win, granule_bytes);
+}
+
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_unpack_marked(
+    uint8_t* __restrict__ dst, const uint8_t* __restrict__ dense,
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule_bytes) {
+  marked_window_walk<false>(dst, const_cast<uint8_t*>(dense), bitmap,
+                            rank_before_word, win, granule_bytes);
+}
+
 // --- persistent service kernel ---------------------------------------------
 //
 // SPDK replaced kernel-driver queues with host polling reactors; the
@@ -2350,6 +2438,459 @@ int bdev_copy_marked_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
   }
   if (status == kIoOk && copied != nullptr) *copied = marked;
   return status;
+}
+
+// ---------------------------------------------------------------------------
+// Marked gather / scatter through a dense staging stream
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint64_t kDefaultStagingHalf = 16ull << 20;
+
+// Per-thread pinned buffers of the pack / unpack calls, grown on demand
+// and kept (see DiffCtx for why nothing is freed per call): the bitmap
+// copy and its exclusive prefix popcount, which the kernels read in
+// place, and the dense staging buffer (two halves on the GPU path).
+struct PackCtx {
+  unsigned long long* words = nullptr;
+  uint32_t* ranks = nullptr;
+  uint64_t word_capacity = 0;
+  uint8_t* staging = nullptr;
+  uint64_t staging_capacity = 0;
+
+  ~PackCtx() {
+    free_pinned(words);
+    free_pinned(ranks);
+    free_pinned(staging);
+  }
+
+  void reserve_words(uint64_t n_words) {
+    if (n_words <= word_capacity) return;
+    free_pinned(words);
+    free_pinned(ranks);
+    words = nullptr;
+    ranks = nullptr;
+    word_capacity = 0;
+    const uint64_t want = std::max<uint64_t>(n_words, 4096);
+    words = static_cast<unsigned long long*>(alloc_pinned(want * 8));
+    ranks = static_cast<uint32_t*>(alloc_pinned(want * 4));
+    if (words == nullptr || ranks == nullptr) {
+      throw std::runtime_error("pack: out of memory");
+    }
+    word_capacity = want;
+  }
+
+  uint8_t* reserve_staging(uint64_t bytes) {
+    if (bytes > staging_capacity) {
+      free_pinned(staging);
+      staging = nullptr;
+      staging_capacity = 0;
+      staging = static_cast<uint8_t*>(alloc_pinned(bytes));
+      if (staging == nullptr) throw std::runtime_error("pack: out of memory");
+      staging_capacity = bytes;
+    }
+    return staging;
+  }
+};
+
+PackCtx& pack_ctx() {
+  thread_local PackCtx ctx;
+  return ctx;
+}
+
+// What both calls and both paths share: the validated geometry, the
+// pinned bitmap copy with stray tail bits cleared, its prefix ranks and
+// the chunk size in granules.
+struct MarkedPlan {
+  uint64_t n_granules = 0;
+  uint64_t n_words = 0;
+  uint64_t marked = 0;
+  uint64_t chunk_granules = 0;
+  unsigned long long* words = nullptr;
+  uint32_t* ranks = nullptr;
+};
+
+int plan_marked(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
+                const std::vector<uint64_t>& bitmap, uint64_t staging_bytes,
+                MarkedPlan* plan) {
+  if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule)) {
+    return kIoInvalid;
+  }
+  plan->n_granules = length / granule;
+  plan->n_words = (plan->n_granules + 63) / 64;
+  if (bitmap.size() < plan->n_words) return kIoInvalid;
+  if (staging_bytes != 0 && staging_bytes < granule) return kIoInvalid;
+  const uint64_t half =
+      staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
+  plan->chunk_granules = std::max<uint64_t>(1, half / granule);
+  PackCtx& ctx = pack_ctx();
+  ctx.reserve_words(plan->n_words);
+  plan->words = ctx.words;
+  plan->ranks = ctx.ranks;
+  uint64_t rank = 0;  // <= kMaxDiffGranules, fits the u32 the kernels read
+  for (uint64_t w = 0; w < plan->n_words; ++w) {
+    unsigned long long word = bitmap[w];
+    const uint64_t left = plan->n_granules - w * 64;
+    if (left < 64) word &= (1ull << left) - 1;
+    plan->words[w] = word;
+    plan->ranks[w] = static_cast<uint32_t>(rank);
+    rank += static_cast<uint64_t>(__builtin_popcountll(word));
+  }
+  plan->marked = rank;
+  plan->chunk_granules = std::min(plan->chunk_granules,
+                                  std::max<uint64_t>(plan->marked, 1));
+  return kIoOk;
+}
+
+// The window that starts at granule `g_begin` and holds the next
+// min(chunk, marks left) marked granules: it ends right after the last
+// of them.
+MarkedWindow next_marked_window(const MarkedPlan& plan, uint64_t g_begin,
+                                uint64_t first_rank) {
+  MarkedWindow win;
+  win.g_begin = g_begin;
+  win.first_rank = static_cast<uint32_t>(first_rank);
+  win.count = static_cast<uint32_t>(
+      std::min(plan.chunk_granules, plan.marked - first_rank));
+  uint64_t need = win.count;
+  uint64_t g_end = g_begin;
+  for (uint64_t w = g_begin / 64; w < plan.n_words && need > 0; ++w) {
+    unsigned long long word = plan.words[w];
+    if (w * 64 < g_begin) word &= ~0ull << (g_begin - w * 64);
+    const uint64_t have = static_cast<uint64_t>(__builtin_popcountll(word));
+    if (have < need) {
+      need -= have;
+      continue;
+    }
+    for (; need > 1; --need) word &= word - 1;
+    g_end = w * 64 + static_cast<uint64_t>(__builtin_ctzll(word)) + 1;
+    need = 0;
+  }
+  win.g_end = g_end;
+  return win;
+}
+
+// One stream and one event per staging half: launch window k+1, then
+// wait for window k only.
+struct MarkedStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t done[2] = {nullptr, nullptr};
+
+  explicit MarkedStream(int device) {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : done) {
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    // Polling elsewhere on this thread leaves hipErrorNotReady behind.
+    (void)hipGetLastError();
+  }
+  ~MarkedStream() {
+    if (stream != nullptr) (void)hipStreamSynchronize(stream);
+    for (hipEvent_t e : done) {
+      if (e != nullptr) (void)hipEventDestroy(e);
+    }
+    if (stream != nullptr) (void)hipStreamDestroy(stream);
+  }
+  MarkedStream(const MarkedStream&) = delete;
+  MarkedStream& operator=(const MarkedStream&) = delete;
+};
+
+// A window's kernel runs for a fraction of a millisecond and the GPU
+// idles until the host has seen it end and launched the window after
+// next, so poll for that long before falling back to a sleeping wait.
+void wait_marked_event(hipEvent_t event) {
+  using clock = std::chrono::steady_clock;
+  const auto give_up = clock::now() + std::chrono::milliseconds(2);
+  hipError_t err = hipEventQuery(event);
+  while (err == hipErrorNotReady && clock::now() < give_up) {
+    err = hipEventQuery(event);
+  }
+  (void)hipGetLastError();  // hipErrorNotReady must not stick
+  if (err == hipErrorNotReady) err = hipEventSynchronize(event);
+  HIP_CHECK(err);
+}
+
+uint32_t marked_window_grid(const MarkedWindow& win) {
+  return granule_grid((win.g_end + 63) / 64 * 64 - win.g_begin / 64 * 64);
+}
+
+int pack_marked_gpu(int device, Bdev* src, uint64_t src_offset,
+                    uint32_t granule, const MarkedPlan& plan,
+                    const PackSink& sink, uint64_t* packed) {
+  const uint64_t half_bytes = plan.chunk_granules * granule;
+  uint8_t* staging = pack_ctx().reserve_staging(2 * half_bytes);
+  MarkedStream ms(device);
+  uint8_t* dev_staging = device_view(staging);
+  const unsigned long long* dev_words = device_view(plan.words);
+  const uint32_t* dev_ranks = device_view(plan.ranks);
+  const uint8_t* base = static_cast<uint8_t*>(src->device_base()) + src_offset;
+  auto launch = [&](const MarkedWindow& win, int half) {
+    hipLaunchKernelGGL(k_pack_marked, dim3(marked_window_grid(win)),
+                       dim3(kWavesPerWg * 64), 0, ms.stream, base,
+                       dev_staging + half * half_bytes, dev_words, dev_ranks,
+                       win, granule);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ms.done[half], ms.stream));
+  };
+  MarkedWindow cur = next_marked_window(plan, 0, 0);
+  launch(cur, 0);
+  for (int half = 0;; half ^= 1) {
+    const uint64_t next_rank = cur.first_rank + static_cast<uint64_t>(cur.count);
+    MarkedWindow next{};
+    if (next_rank < plan.marked) {
+      next = next_marked_window(plan, cur.g_end, next_rank);
+      launch(next, half ^ 1);
+    }
+    wait_marked_event(ms.done[half]);
+    const int status =
+        sink(staging + half * half_bytes, cur.first_rank, cur.count);
+    if (status != 0) return status;
+    *packed = next_rank;
+    if (next_rank >= plan.marked) return kIoOk;
+    cur = next;
+  }
+}
+
+int unpack_marked_gpu(int device, Bdev* dst, uint64_t dst_offset,
+                      uint32_t granule, const MarkedPlan& plan,
+                      const UnpackSource& source, uint64_t* unpacked) {
+  const uint64_t half_bytes = plan.chunk_granules * granule;
+  uint8_t* staging = pack_ctx().reserve_staging(2 * half_bytes);
+  MarkedStream ms(device);
+  const uint8_t* dev_staging = device_view(staging);
+  const unsigned long long* dev_words = device_view(plan.words);
+  const uint32_t* dev_ranks = device_view(plan.ranks);
+  uint8_t* base = static_cast<uint8_t*>(dst->device_base()) + dst_offset;
+  bool used[2] = {false, false};
+  uint64_t g_begin = 0;
+  uint64_t launched = 0;
+  for (int half = 0; launched < plan.marked; half ^= 1) {
+    const MarkedWindow win = next_marked_window(plan, g_begin, launched);
+    // The kernel two windows back read this half: let it finish first.
+    if (used[half]) wait_marked_event(ms.done[half]);
+    const int status =
+        source(staging + half * half_bytes, win.first_rank, win.count);
+    if (status != 0) {
+      HIP_CHECK(hipStreamSynchronize(ms.stream));
+      *unpacked = launched;
+      return status;
+    }
+    hipLaunchKernelGGL(k_unpack_marked, dim3(marked_window_grid(win)),
+                       dim3(kWavesPerWg * 64), 0, ms.stream, base,
+                       dev_staging + half * half_bytes, dev_words, dev_ranks,
+                       win, granule);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ms.done[half], ms.stream));
+    used[half] = true;
+    launched += win.count;
+    g_begin = win.g_end;
+  }
+  HIP_CHECK(hipStreamSynchronize(ms.stream));
+  *unpacked = launched;
+  return kIoOk;
+}
+
+// Generic path: the same chunks, filled from (or drained to) runs of
+// marked granules in spans of at most 1 MiB.
+template <typename Chunk>
+int marked_generic(Bdev* bdev, uint64_t offset, uint32_t granule,
+                   const MarkedPlan& plan, bool pack, Chunk chunk,
+                   uint64_t* moved) {
+  uint8_t* buf = pack_ctx().reserve_staging(plan.chunk_granules * granule);
+  const uint64_t span = host_chunk_bytes(bdev);
+  auto marked_at = [&plan](uint64_t g) {
+    return (plan.words[g / 64] >> (g % 64)) & 1;
+  };
+  uint64_t g = 0;
+  for (uint64_t first_rank = 0; first_rank < plan.marked;) {
+    const uint64_t count =
+        std::min(plan.chunk_granules, plan.marked - first_rank);
+    if (!pack) {
+      const int status = chunk(buf, first_rank, count);
+      if (status != 0) return status;
+    }
+    for (uint64_t filled = 0; filled < count;) {
+      while (!marked_at(g)) ++g;
+      uint64_t end = g + 1;
+      while (end < plan.n_granules && end - g < count - filled &&
+             marked_at(end)) {
+        ++end;
+      }
+      const uint64_t bytes = (end - g) * granule;
+      for (uint64_t pos = 0; pos < bytes; pos += span) {
+        const uint64_t n = std::min(span, bytes - pos);
+        uint8_t* p = buf + filled * granule + pos;
+        const uint64_t at = offset + g * granule + pos;
+        const int status = pack ? bdev_read_sync(bdev, at, p, n)
+                                : bdev_write_sync(bdev, at, p, n);
+        if (status != kIoOk) return status;
+      }
+      filled += end - g;
+      g = end;
+    }
+    if (pack) {
+      const int status = chunk(buf, first_rank, count);
+      if (status != 0) return status;
+    }
+    first_rank += count;
+    *moved = first_rank;
+  }
+  return kIoOk;
+}
+
+int marked_kernel_device(Bdev* bdev) {
+  return granule_kernel_device(bdev, bdev);
+}
+
+}  // namespace
+
+int bdev_pack_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
+                          uint32_t granule,
+                          const std::vector<uint64_t>& bitmap,
+                          uint64_t staging_bytes, const PackSink& sink,
+                          uint64_t* packed) {
+  uint64_t moved = 0;
+  if (packed != nullptr) *packed = 0;
+  int status;
+  try {
+    MarkedPlan plan;
+    status = plan_marked(src, src_offset, length, granule, bitmap,
+                         staging_bytes, &plan);
+    if (status != kIoOk || plan.marked == 0) return status;
+    if (!sink) return kIoInvalid;
+    const int device = marked_kernel_device(src);
+    if (device >= 0) {
+      status = pack_marked_gpu(device, src, src_offset, granule, plan, sink,
+                               &moved);
+    } else {
+      status = marked_generic(src, src_offset, granule, plan, true, sink,
+                              &moved);
+    }
+  } catch (const std::exception&) {
+    status = kIoFailed;
+  }
+  if (packed != nullptr) *packed = moved;
+  return status;
+}
+
+int bdev_unpack_marked_sync(Bdev* dst, uint64_t dst_offset, uint64_t length,
+                            uint32_t granule,
+                            const std::vector<uint64_t>& bitmap,
+                            uint64_t staging_bytes,
+                            const UnpackSource& source, uint64_t* unpacked) {
+  uint64_t moved = 0;
+  if (unpacked != nullptr) *unpacked = 0;
+  int status;
+  try {
+    MarkedPlan plan;
+    status = plan_marked(dst, dst_offset, length, granule, bitmap,
+                         staging_bytes, &plan);
+    if (status != kIoOk || plan.marked == 0) return status;
+    if (!source) return kIoInvalid;
+    const int device = marked_kernel_device(dst);
+    if (device >= 0) {
+      status = unpack_marked_gpu(device, dst, dst_offset, granule, plan,
+                                 source, &moved);
+    } else {
+      status = marked_generic(dst, dst_offset, granule, plan, false, source,
+                              &moved);
+    }
+  } catch (const std::exception&) {
+    status = kIoFailed;
+  }
+  if (unpacked != nullptr) *unpacked = moved;
+  return status;
+}
+
+// Measurement aid (tools/delta_bench.py): times, on the host clock from
+// the first enqueue to the end of a stream synchronise, what moves the
+// marked bytes of an HBM bdev to pinned host memory.
+//   mode 0: hipMemcpyAsync of the same byte count from the start of the
+//           volume, in pieces as large as the pinned buffer (PCIe ceiling)
+//   mode 1: one hipMemcpyAsync per run of marked granules (what
+//           k_pack_marked replaces)
+//   mode 2: bdev_pack_marked_sync with a sink that discards
+// Modes 0 and 1 land in a pinned ring of at most `ring_bytes`; a run
+// that would cross its end is split there.
+int marked_copy_probe(Bdev* src, uint32_t granule,
+                      const std::vector<uint64_t>& bitmap, int mode,
+                      uint64_t ring_bytes, uint64_t staging_bytes,
+                      MarkedCopyProbe* out) {
+  using clock = std::chrono::steady_clock;
+  *out = MarkedCopyProbe{};
+  if (src == nullptr || mode < 0 || mode > 2) return kIoInvalid;
+  const uint64_t length = src->size_bytes() / std::max(granule, 1u) * granule;
+  if (mode == 2) {
+    const auto t0 = clock::now();
+    const int status = bdev_pack_marked_sync(
+        src, 0, length, granule, bitmap, staging_bytes,
+        [out](const uint8_t*, uint64_t, uint64_t) {
+          ++out->calls;
+          return 0;
+        },
+        &out->granules);
+    out->seconds = std::chrono::duration<double>(clock::now() - t0).count();
+    return status;
+  }
+  try {
+    MarkedPlan plan;
+    const int status = plan_marked(src, 0, length, granule, bitmap, 0, &plan);
+    if (status != kIoOk) return status;
+    const int device = marked_kernel_device(src);
+    if (device < 0 || plan.marked == 0 || ring_bytes < granule) {
+      return kIoInvalid;
+    }
+    const uint64_t total = plan.marked * granule;
+    const uint64_t ring = std::min(ring_bytes / granule * granule, total);
+    HIP_CHECK(hipSetDevice(device));
+    uint8_t* pinned = static_cast<uint8_t*>(alloc_pinned(ring));
+    if (pinned == nullptr) return kIoFailed;
+    memset(pinned, 0, ring);  // touch every page before the clock starts
+    hipStream_t stream = nullptr;
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    const uint8_t* base = static_cast<uint8_t*>(src->device_base());
+    uint64_t at = 0;  // write position in the ring
+    auto copy = [&](uint64_t from, uint64_t bytes) {
+      while (bytes > 0) {
+        const uint64_t n = std::min(bytes, ring - at);
+        HIP_CHECK(hipMemcpyAsync(pinned + at, base + from, n,
+                                 hipMemcpyDeviceToHost, stream));
+        ++out->calls;
+        at = (at + n) % ring;
+        from += n;
+        bytes -= n;
+      }
+    };
+    const auto t0 = clock::now();
+    if (mode == 0) {
+      copy(0, total);
+    } else {
+      for (uint64_t g = 0; g < plan.n_granules;) {
+        if (((plan.words[g / 64] >> (g % 64)) & 1) == 0) {
+          // a zero word is skipped whole
+          g += (g % 64 == 0 && plan.words[g / 64] == 0) ? 64 : 1;
+          continue;
+        }
+        uint64_t end = g + 1;
+        while (end < plan.n_granules &&
+               ((plan.words[end / 64] >> (end % 64)) & 1)) {
+          ++end;
+        }
+        copy(g * granule, (end - g) * granule);
+        g = end;
+      }
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    out->seconds = std::chrono::duration<double>(clock::now() - t0).count();
+    out->granules = plan.marked;
+    (void)hipStreamDestroy(stream);
+    free_pinned(pinned);
+    return kIoOk;
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
 }
 
 // ---------------------------------------------------------------------------

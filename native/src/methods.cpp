@@ -14,6 +14,7 @@
 
 #include "hipstore/bdev.h"
 #include "hipstore/composite.h"
+#include "hipstore/delta.h"
 #include "hipstore/engine.h"
 #include "hipstore/json.h"
 #include "hipstore/nbd.h"
@@ -1074,6 +1075,67 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(r.granule));
         o["replicas"] = Json(std::move(replicas));
+        return Json(std::move(o));
+      });
+
+  // --- checkpoints to files (native extensions) ----------------------------
+  // kIoInvalid (parameters, geometry, malformed or corrupt file) is
+  // -32602; everything else (I/O, claimed target, existing file) -32603.
+  auto delta_error = [](const char* method, int status,
+                        const std::string& why) {
+    return RpcError{status == kIoInvalid ? kInvalidParams : kInternalError,
+                    std::string(method) + ": " + why};
+  };
+
+  server->register_method(
+      "bdev_export_delta", [&manager, granule_param, delta_error](const Json& p) {
+        // Writes a volume, or with "base" its difference from an earlier
+        // clone, to a delta file (HBM volumes leave through
+        // k_pack_marked, one launch per staging window).
+        const std::string name = p.get_string("name");
+        BdevPtr src = manager.find(name);
+        if (!src) not_found("bdev " + name);
+        BdevPtr base;
+        if (p.has("base")) {
+          base = manager.find(p.get_string("base"));
+          if (!base) not_found("bdev " + p.get_string("base"));
+        }
+        const std::string path = p.get_string("path");
+        if (path.empty()) throw RpcError{kInvalidParams, "path required"};
+        const uint32_t granule = granule_param(p, src);
+        DeltaInfo info;
+        std::string why;
+        const int status =
+            bdev_export_delta(src.get(), base.get(), path, granule,
+                              p.get_bool("overwrite", false), &info, &why);
+        if (status != kIoOk) throw delta_error("bdev_export_delta", status, why);
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(info.granule));
+        o["granules"] = Json(static_cast<int64_t>(info.n_granules));
+        o["saved"] = Json(static_cast<int64_t>(info.n_marked));
+        o["file_bytes"] = Json(static_cast<int64_t>(info.file_bytes));
+        o["full"] = Json(info.full);
+        return Json(std::move(o));
+      });
+
+  server->register_method(
+      "bdev_import_delta", [&manager, delta_error](const Json& p) {
+        // Applies a delta file to a volume; offline only, like repair
+        // and resize. dry_run checks every CRC and writes nothing.
+        const std::string name = p.get_string("name");
+        BdevPtr dst = manager.find(name);
+        if (!dst) not_found("bdev " + name);
+        const std::string path = p.get_string("path");
+        if (path.empty()) throw RpcError{kInvalidParams, "path required"};
+        DeltaInfo info;
+        std::string why;
+        const int status = bdev_import_delta(
+            dst.get(), path, p.get_bool("dry_run", false), &info, &why);
+        if (status != kIoOk) throw delta_error("bdev_import_delta", status, why);
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(info.granule));
+        o["granules"] = Json(static_cast<int64_t>(info.n_granules));
+        o["applied"] = Json(static_cast<int64_t>(info.n_marked));
         return Json(std::move(o));
       });
 

@@ -10,11 +10,13 @@
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <optional>
 #include <stdexcept>
 
 #include "hipstore/bdev.h"
 #include "hipstore/composite.h"
 #include "hipstore/crc32c.h"
+#include "hipstore/delta.h"
 #include "hipstore/engine.h"
 #include "hipstore/nvmf.h"
 #include "hipstore/rados.h"
@@ -122,6 +124,59 @@ py::dict perf_to_dict(const PerfResult& r) {
   d["lat_p999_us"] = r.lat_p999_us;
   d["lat_max_us"] = r.lat_max_us;
   return d;
+}
+
+// Bitmap bytes (granule g is byte g//8, bit g%8) -> bdev_diff_sync words.
+std::vector<uint64_t> bitmap_words(const std::string& raw) {
+  std::vector<uint64_t> words((raw.size() + 7) / 8, 0);
+  for (size_t i = 0; i < raw.size(); ++i) {
+    words[i / 8] |= static_cast<uint64_t>(static_cast<uint8_t>(raw[i]))
+                    << (8 * (i % 8));
+  }
+  return words;
+}
+
+// Range of the pack / unpack bindings: length None = to the end of the
+// device, rounded down to whole granules. Throws when the bitmap does
+// not cover it; the core validates the rest.
+uint64_t marked_range(const char* what, Bdev& bdev, uint64_t offset,
+                      std::optional<uint64_t> length, uint32_t granule,
+                      const std::string& bitmap) {
+  uint64_t len = 0;
+  if (length) {
+    len = *length;
+  } else if (granule != 0 && offset <= bdev.size_bytes()) {
+    len = (bdev.size_bytes() - offset) / granule * granule;
+  }
+  if (granule != 0) {
+    const uint64_t n_granules = len / granule;
+    if (bitmap.size() < n_granules / 8 + (n_granules % 8 != 0)) {
+      throw std::runtime_error(std::string(what) +
+                               ": bitmap shorter than range");
+    }
+  }
+  return len;
+}
+
+py::dict delta_info_to_dict(const DeltaInfo& info) {
+  py::dict d;
+  d["version"] = info.version;
+  d["block_size"] = info.block_size;
+  d["granule"] = info.granule;
+  d["full"] = info.full;
+  d["volume_bytes"] = info.volume_bytes;
+  d["granules"] = info.n_granules;
+  d["marked"] = info.n_marked;
+  d["file_bytes"] = info.file_bytes;
+  return d;
+}
+
+[[noreturn]] void throw_delta(const char* what, int status,
+                              const std::string& error) {
+  const std::string text = std::string(what) + ": " + error + " (status " +
+                           std::to_string(status) + ")";
+  if (status == kIoInvalid) throw std::invalid_argument(text);
+  throw std::runtime_error(text);
 }
 
 }  // namespace
@@ -362,6 +417,150 @@ PYBIND11_MODULE(_hipstore, m) {
      py::arg("length") = 0,
      "Copy only the granules marked in `bitmap` (bdev_diff layout); "
      "returns the number copied");
+
+  m.def("bdev_pack_marked", [](BdevPtr src, py::bytes bitmap, uint32_t granule,
+                               uint64_t src_offset,
+                               std::optional<uint64_t> length,
+                               uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len = marked_range("bdev_pack_marked", *src, src_offset,
+                                      length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    std::string out;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_pack_marked_sync(
+          src.get(), src_offset, len, granule, words, staging_bytes,
+          [&out, granule](const uint8_t* data, uint64_t, uint64_t count) {
+            out.append(reinterpret_cast<const char*>(data), count * granule);
+            return 0;
+          });
+    }
+    if (status != kIoOk) {
+      throw std::runtime_error("bdev_pack_marked failed: status " +
+                               std::to_string(status));
+    }
+    return py::bytes(out);
+  }, py::arg("src"), py::arg("bitmap"), py::arg("granule"),
+     py::arg("src_offset") = 0, py::arg("length") = py::none(),
+     py::arg("staging_bytes") = 0,
+     "Gather the granules marked in `bitmap` (bdev_diff layout) into one "
+     "dense bytes object, ascending (on-GPU for HBM bdevs)");
+
+  m.def("bdev_unpack_marked", [](BdevPtr dst, py::bytes bitmap,
+                                 uint32_t granule, py::bytes data,
+                                 uint64_t dst_offset,
+                                 std::optional<uint64_t> length,
+                                 uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len = marked_range("bdev_unpack_marked", *dst, dst_offset,
+                                      length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    const std::string dense = data;
+    if (granule != 0) {
+      uint64_t marked = 0;
+      for (uint64_t g = 0; g < len / granule; ++g) {
+        marked += (words[g / 64] >> (g % 64)) & 1;
+      }
+      if (dense.size() != marked * granule) {
+        throw std::runtime_error(
+            "bdev_unpack_marked: data length " + std::to_string(dense.size()) +
+            " is not marked * granule = " + std::to_string(marked * granule));
+      }
+    }
+    uint64_t unpacked = 0;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_unpack_marked_sync(
+          dst.get(), dst_offset, len, granule, words, staging_bytes,
+          [&dense, granule](uint8_t* out, uint64_t first_rank,
+                            uint64_t count) {
+            memcpy(out, dense.data() + first_rank * granule, count * granule);
+            return 0;
+          },
+          &unpacked);
+    }
+    if (status != kIoOk) {
+      throw std::runtime_error("bdev_unpack_marked failed: status " +
+                               std::to_string(status));
+    }
+    return unpacked;
+  }, py::arg("dst"), py::arg("bitmap"), py::arg("granule"), py::arg("data"),
+     py::arg("dst_offset") = 0, py::arg("length") = py::none(),
+     py::arg("staging_bytes") = 0,
+     "Scatter a dense bytes object to the granules marked in `bitmap`; "
+     "returns the number written");
+
+  m.def("marked_copy_probe", [](BdevPtr src, py::bytes bitmap,
+                                uint32_t granule, int mode,
+                                uint64_t ring_bytes, uint64_t staging_bytes) {
+    const std::vector<uint64_t> words = bitmap_words(bitmap);
+    MarkedCopyProbe probe;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = marked_copy_probe(src.get(), granule, words, mode, ring_bytes,
+                                 staging_bytes, &probe);
+    }
+    if (status != kIoOk) {
+      throw std::runtime_error("marked_copy_probe failed: status " +
+                               std::to_string(status));
+    }
+    py::dict d;
+    d["seconds"] = probe.seconds;
+    d["granules"] = probe.granules;
+    d["calls"] = probe.calls;
+    return d;
+  }, py::arg("src"), py::arg("bitmap"), py::arg("granule"), py::arg("mode"),
+     py::arg("ring_bytes") = 1ull << 30, py::arg("staging_bytes") = 0,
+     "Measurement aid (tools/delta_bench.py): marked bytes to pinned host "
+     "memory by one hipMemcpyAsync (0), one per run (1) or the pack "
+     "kernel with a discarding sink (2)");
+
+  m.def("bdev_export_delta", [](BdevPtr src, const std::string& path,
+                                std::optional<BdevPtr> base,
+                                std::optional<uint32_t> granule,
+                                bool overwrite) {
+    DeltaInfo info;
+    std::string error;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_export_delta(src.get(), base ? base->get() : nullptr,
+                                 path, granule.value_or(0), overwrite, &info,
+                                 &error);
+    }
+    if (status != kIoOk) throw_delta("bdev_export_delta", status, error);
+    return delta_info_to_dict(info);
+  }, py::arg("src"), py::arg("path"), py::arg("base") = py::none(),
+     py::arg("granule") = py::none(), py::arg("overwrite") = false,
+     "Write the granules of src that differ from base (every granule "
+     "without a base) to a hipstore delta file");
+
+  m.def("bdev_import_delta", [](BdevPtr dst, const std::string& path,
+                                bool dry_run) {
+    DeltaInfo info;
+    std::string error;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_import_delta(dst.get(), path, dry_run, &info, &error);
+    }
+    if (status != kIoOk) throw_delta("bdev_import_delta", status, error);
+    return delta_info_to_dict(info);
+  }, py::arg("dst"), py::arg("path"), py::arg("dry_run") = false,
+     "Apply a hipstore delta file to dst; dry_run checks everything and "
+     "writes nothing");
+
+  m.def("delta_file_info", [](const std::string& path) {
+    DeltaInfo info;
+    std::string error;
+    const int status = delta_file_info(path, &info, &error);
+    if (status != kIoOk) throw_delta("delta_file_info", status, error);
+    return delta_info_to_dict(info);
+  }, py::arg("path"), "Header fields of a delta file, after its structural checks");
 
   m.def("replica_scrub", [](BdevPtr bdev, bool repair, uint32_t granule,
                             uint32_t max_report) {

@@ -8,6 +8,8 @@ extended with proxied volume operations).
   oimctl ... map --controller gpu-0 vol1
   oimctl ... unmap --controller gpu-0 vol1
   oimctl ... check --controller gpu-0 vol1
+  oimctl ... checkpoint --controller gpu-0 vol1 /backup/vol1.d1 --base vol1-snap
+  oimctl ... restore --controller gpu-0 vol1 /backup/vol1.full
 """
 
 import argparse
@@ -41,6 +43,9 @@ def main(argv=None) -> int:
         ("check", "check that a malloc bdev exists"),
         ("clone", "clone a malloc bdev (device-side HBM-rate copy)"),
         ("resize", "grow a malloc bdev (offline)"),
+        ("checkpoint", "write a malloc bdev (or its difference from "
+         "--base) to a delta file"),
+        ("restore", "apply a delta file to an unmapped malloc bdev"),
         ("list", "list malloc bdevs"),
         ("stats", "per-bdev I/O counters"),
     ):
@@ -59,6 +64,16 @@ def main(argv=None) -> int:
             cmd.add_argument("dest", help="name of the clone to create")
         if name == "resize":
             cmd.add_argument("size", help='new size: bytes or "8GiB"-style')
+        if name in ("checkpoint", "restore"):
+            cmd.add_argument("path", help="delta file on the controller's "
+                             "host")
+        if name == "checkpoint":
+            cmd.add_argument("--base", default="",
+                             help="earlier clone: save only what differs")
+            cmd.add_argument("--overwrite", action="store_true")
+        if name == "restore":
+            cmd.add_argument("--dry-run", action="store_true",
+                             help="check the file, write nothing")
     args = parser.parse_args(argv)
     log.init_from_args(args)
 
@@ -135,6 +150,24 @@ def main(argv=None) -> int:
                           f"writes={st.num_write_ops} "
                           f"unmaps={st.num_unmap_ops} "
                           f"rB={st.bytes_read} wB={st.bytes_written}")
+            elif args.command == "checkpoint":
+                reply = controller.CheckpointMallocBDev(
+                    spec.CheckpointMallocBDevRequest(
+                        bdev_name=args.volume, base_name=args.base,
+                        path=args.path, overwrite=args.overwrite),
+                    metadata=metadata, timeout=600)
+                print(f"checkpointed {args.volume} -> {args.path}: "
+                      f"{reply.saved} of {reply.granules} granules, "
+                      f"{reply.file_bytes} bytes")
+            elif args.command == "restore":
+                reply = controller.RestoreMallocBDev(
+                    spec.RestoreMallocBDevRequest(
+                        bdev_name=args.volume, path=args.path,
+                        dry_run=args.dry_run),
+                    metadata=metadata, timeout=600)
+                verb = "verified" if args.dry_run else "restored"
+                print(f"{verb} {args.volume} <- {args.path}: "
+                      f"{reply.applied} of {reply.granules} granules")
             elif args.command == "resize":
                 new_size = parse_size(args.size)
                 controller.ResizeMallocBDev(

@@ -374,6 +374,68 @@ class Controller(spec.ControllerServicer):
                     context.abort(grpc.StatusCode.INTERNAL, str(err))
         return spec.ResizeMallocBDevReply()
 
+    def _require_bdev(self, client, name, context):
+        try:
+            hipstore.get_bdevs(client, name)
+        except hipstore.RpcError as err:
+            if err.is_not_found():
+                context.abort(grpc.StatusCode.NOT_FOUND,
+                              f"BDev {name} not found")
+            context.abort(grpc.StatusCode.INTERNAL, str(err))
+
+    @staticmethod
+    def _abort_delta(context, err):
+        """bdev_export_delta / bdev_import_delta errors: -32602 is bad
+        input (parameters, geometry, corrupt file); a claimed target
+        and an existing file are preconditions the caller can fix."""
+        if err.code == hipstore.ERROR_INVALID_PARAMS:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT, str(err))
+        if "is claimed" in str(err):
+            context.abort(grpc.StatusCode.FAILED_PRECONDITION, str(err))
+        if "exists (overwrite not set)" in str(err):
+            context.abort(grpc.StatusCode.ALREADY_EXISTS, str(err))
+        context.abort(grpc.StatusCode.INTERNAL, str(err))
+
+    def CheckpointMallocBDev(self, request, context):
+        """oim-amd extension (docs/spec.md): write a volume, or its
+        difference from an earlier clone, to a delta file."""
+        name, base, path = request.bdev_name, request.base_name, request.path
+        if not name or not path:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          "bdev_name and path are required")
+        with self._volume_mutex.locked(name):
+            with self._client() as client:
+                self._require_bdev(client, name, context)
+                if base:
+                    self._require_bdev(client, base, context)
+                try:
+                    result = hipstore.bdev_export_delta(
+                        client, name, path, base=base or None,
+                        overwrite=request.overwrite)
+                except hipstore.RpcError as err:
+                    self._abort_delta(context, err)
+        return spec.CheckpointMallocBDevReply(
+            granules=result["granules"], saved=result["saved"],
+            file_bytes=result["file_bytes"])
+
+    def RestoreMallocBDev(self, request, context):
+        """oim-amd extension (docs/spec.md): apply a delta file to an
+        unmapped volume."""
+        name, path = request.bdev_name, request.path
+        if not name or not path:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          "bdev_name and path are required")
+        with self._volume_mutex.locked(name):
+            with self._client() as client:
+                self._require_bdev(client, name, context)
+                try:
+                    result = hipstore.bdev_import_delta(
+                        client, name, path, dry_run=request.dry_run)
+                except hipstore.RpcError as err:
+                    self._abort_delta(context, err)
+        return spec.RestoreMallocBDevReply(granules=result["granules"],
+                                           applied=result["applied"])
+
     def ListMallocBDevs(self, request, context):
         """oim-amd extension (docs/spec.md): enumerate malloc bdevs."""
         reply = spec.ListMallocBDevsReply()

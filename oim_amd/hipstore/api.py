@@ -272,6 +272,37 @@ def bdev_replica_scrub(client: Client, name: str, repair: bool = False,
     return client.invoke("bdev_replica_scrub", params)
 
 
+def bdev_export_delta(client: Client, name: str, path: str,
+                      base: Optional[str] = None,
+                      granule: Optional[int] = None,
+                      overwrite: bool = False) -> Dict:
+    """Checkpoint a volume to a delta file: every granule, or with
+    `base` (an earlier clone) only the granules that differ from it.
+
+    Returns {granule, granules, saved, file_bytes, full}. granule
+    defaults to the block size."""
+    params: Dict = {"name": name, "path": path}
+    if base is not None:
+        params["base"] = base
+    if granule is not None:
+        params["granule"] = granule
+    if overwrite:
+        params["overwrite"] = True
+    return client.invoke("bdev_export_delta", params)
+
+
+def bdev_import_delta(client: Client, name: str, path: str,
+                      dry_run: bool = False) -> Dict:
+    """Apply a delta file to an unclaimed volume; dry_run checks the
+    file (every CRC) and writes nothing.
+
+    Returns {granule, granules, applied}."""
+    params: Dict = {"name": name, "path": path}
+    if dry_run:
+        params["dry_run"] = True
+    return client.invoke("bdev_import_delta", params)
+
+
 def resize_malloc_bdev(client: Client, name: str, size: int) -> int:
     """Offline resize to `size` bytes; returns the new block count."""
     return client.invoke("resize_malloc_bdev",

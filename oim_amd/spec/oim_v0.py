@@ -71,6 +71,17 @@ MESSAGES = [
     Message("ResizeMallocBDevRequest",
             [Field("bdev_name", 1, "string"), Field("size", 2, "int64")]),
     Message("ResizeMallocBDevReply", []),
+    Message("CheckpointMallocBDevRequest",
+            [Field("bdev_name", 1, "string"), Field("base_name", 2, "string"),
+             Field("path", 3, "string"), Field("overwrite", 4, "bool")]),
+    Message("CheckpointMallocBDevReply",
+            [Field("granules", 1, "int64"), Field("saved", 2, "int64"),
+             Field("file_bytes", 3, "int64")]),
+    Message("RestoreMallocBDevRequest",
+            [Field("bdev_name", 1, "string"), Field("path", 2, "string"),
+             Field("dry_run", 3, "bool")]),
+    Message("RestoreMallocBDevReply",
+            [Field("granules", 1, "int64"), Field("applied", 2, "int64")]),
     Message("ListMallocBDevsRequest", [Field("prefix", 1, "string")]),
     Message("BDevInfo",
             [Field("name", 1, "string"), Field("size", 2, "int64"),
@@ -107,6 +118,8 @@ SERVICES = [
             ("CheckMallocBDev", "CheckMallocBDevRequest", "CheckMallocBDevReply"),
             ("CloneMallocBDev", "CloneMallocBDevRequest", "CloneMallocBDevReply"),
             ("ResizeMallocBDev", "ResizeMallocBDevRequest", "ResizeMallocBDevReply"),
+            ("CheckpointMallocBDev", "CheckpointMallocBDevRequest", "CheckpointMallocBDevReply"),
+            ("RestoreMallocBDev", "RestoreMallocBDevRequest", "RestoreMallocBDevReply"),
             ("ListMallocBDevs", "ListMallocBDevsRequest", "ListMallocBDevsReply"),
             ("GetIOStats", "GetIOStatsRequest", "GetIOStatsReply"),
         ],
@@ -138,6 +151,10 @@ CloneMallocBDevRequest = _classes["CloneMallocBDevRequest"]
 CloneMallocBDevReply = _classes["CloneMallocBDevReply"]
 ResizeMallocBDevRequest = _classes["ResizeMallocBDevRequest"]
 ResizeMallocBDevReply = _classes["ResizeMallocBDevReply"]
+CheckpointMallocBDevRequest = _classes["CheckpointMallocBDevRequest"]
+CheckpointMallocBDevReply = _classes["CheckpointMallocBDevReply"]
+RestoreMallocBDevRequest = _classes["RestoreMallocBDevRequest"]
+RestoreMallocBDevReply = _classes["RestoreMallocBDevReply"]
 ListMallocBDevsRequest = _classes["ListMallocBDevsRequest"]
 BDevInfo = _classes["BDevInfo"]
 ListMallocBDevsReply = _classes["ListMallocBDevsReply"]

@@ -50,6 +50,10 @@ class ControllerStub:
         self.CheckMallocBDev = method("CheckMallocBDev", pb.CheckMallocBDevReply)
         self.CloneMallocBDev = method("CloneMallocBDev", pb.CloneMallocBDevReply)
         self.ResizeMallocBDev = method("ResizeMallocBDev", pb.ResizeMallocBDevReply)
+        self.CheckpointMallocBDev = method(
+            "CheckpointMallocBDev", pb.CheckpointMallocBDevReply)
+        self.RestoreMallocBDev = method(
+            "RestoreMallocBDev", pb.RestoreMallocBDevReply)
         self.ListMallocBDevs = method("ListMallocBDevs", pb.ListMallocBDevsReply)
         self.GetIOStats = method("GetIOStats", pb.GetIOStatsReply)
 
@@ -84,6 +88,12 @@ class ControllerServicer:
 
     def ResizeMallocBDev(self, request, context):
         context.abort(grpc.StatusCode.UNIMPLEMENTED, "ResizeMallocBDev not implemented")
+
+    def CheckpointMallocBDev(self, request, context):
+        context.abort(grpc.StatusCode.UNIMPLEMENTED, "CheckpointMallocBDev not implemented")
+
+    def RestoreMallocBDev(self, request, context):
+        context.abort(grpc.StatusCode.UNIMPLEMENTED, "RestoreMallocBDev not implemented")
 
     def ListMallocBDevs(self, request, context):
         context.abort(grpc.StatusCode.UNIMPLEMENTED, "ListMallocBDevs not implemented")
@@ -120,6 +130,10 @@ def add_controller_to_server(servicer: ControllerServicer, server: grpc.Server) 
         "CheckMallocBDev": _unary(servicer.CheckMallocBDev, pb.CheckMallocBDevRequest),
         "CloneMallocBDev": _unary(servicer.CloneMallocBDev, pb.CloneMallocBDevRequest),
         "ResizeMallocBDev": _unary(servicer.ResizeMallocBDev, pb.ResizeMallocBDevRequest),
+        "CheckpointMallocBDev": _unary(
+            servicer.CheckpointMallocBDev, pb.CheckpointMallocBDevRequest),
+        "RestoreMallocBDev": _unary(
+            servicer.RestoreMallocBDev, pb.RestoreMallocBDevRequest),
         "ListMallocBDevs": _unary(servicer.ListMallocBDevs, pb.ListMallocBDevsRequest),
         "GetIOStats": _unary(servicer.GetIOStats, pb.GetIOStatsRequest),
     }
