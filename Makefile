@@ -18,12 +18,13 @@ LDLIBS := -L$(ROCM)/lib -lrccl
 
 B := native/build
 HDRS := $(wildcard native/include/hipstore/*.h)
+HIP_HDRS := $(HDRS) native/src/gpu_internal.h
 
 CORE_OBJS := $(B)/json.o $(B)/bdev.o $(B)/crc32c.o $(B)/rpc_server.o \
              $(B)/methods.o $(B)/nbd.o $(B)/ublk.o $(B)/composite.o $(B)/vhost.o $(B)/vhost_master.o \
              $(B)/nvmf_common.o $(B)/nvmf_target.o $(B)/nvmf_initiator.o \
              $(B)/rados_client.o $(B)/rados_cluster.o $(B)/delta.o \
-             $(B)/gpu.o
+             $(B)/gpu.o $(B)/bulk_ops.o
 
 .PHONY: all clean
 all: oim_amd/_hipstore$(EXT_SUFFIX) bin/hipstored
@@ -34,7 +35,7 @@ $(B):
 $(B)/%.o: native/src/%.cpp $(HDRS) | $(B)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
-$(B)/gpu.o: native/src/gpu.hip $(HDRS) | $(B)
+$(B)/%.o: native/src/%.hip $(HIP_HDRS) | $(B)
 	$(HIPCC) $(CXXFLAGS) $(HIPFLAGS) -c $< -o $@
 
 $(B)/pybind.o: native/src/pybind.cpp $(HDRS) | $(B)
@@ -60,7 +61,7 @@ $(B)/asan:
 $(B)/asan/%.o: native/src/%.cpp $(HDRS) | $(B)/asan
 	$(HIPCC) $(CXXFLAGS) $(ASAN_FLAGS) -c $< -o $@
 
-$(B)/asan/gpu.o: native/src/gpu.hip $(HDRS) | $(B)/asan
+$(B)/asan/%.o: native/src/%.hip $(HIP_HDRS) | $(B)/asan
 	$(HIPCC) $(CXXFLAGS) $(ASAN_FLAGS) $(HIPFLAGS) -c $< -o $@
 
 .PHONY: asan

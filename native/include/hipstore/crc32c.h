@@ -32,6 +32,7 @@ uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, size_t len2);
 // Per-block CRC32C of `count` consecutive `block_size`-byte blocks
 // starting at byte `offset` of the bdev. HBM bdevs compute on-GPU;
 // other bdevs fall back to reading + software CRC (CI path).
+// Implemented in bulk_ops.hip, like crc32c_hbm_range.
 void crc32c_hbm_blocks(Bdev* bdev, uint64_t offset, uint32_t block_size,
                        uint32_t count, uint32_t* out);
 

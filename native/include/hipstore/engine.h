@@ -1,4 +1,7 @@
-// GPU data-path engine API (implemented in gpu.hip).
+// GPU data-path engine API. The engines, bdev creation, the pinned
+// helpers, the sync wrappers, IoQueue and bdevperf are implemented in
+// gpu.hip; hbm_copy_sync and the bdev_diff / copy_marked / pack_marked /
+// unpack_marked calls (and marked_copy_probe) in bulk_ops.hip.
 //
 // MI355X-native replacement for the reference's SPDK copy engine +
 // malloc bdev pair (reference lib/copy/copy_engine.c,

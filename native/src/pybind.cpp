@@ -136,9 +136,21 @@ std::vector<uint64_t> bitmap_words(const std::string& raw) {
   return words;
 }
 
+// Throws when `bitmap` (bytes) does not cover `length / granule`
+// granules; the core validates the rest.
+void check_bitmap_covers(const char* what, uint64_t length, uint32_t granule,
+                         const std::string& bitmap) {
+  if (granule == 0) return;
+  const uint64_t n_granules = length / granule;
+  if (bitmap.size() < n_granules / 8 + (n_granules % 8 != 0)) {
+    throw std::runtime_error(std::string(what) +
+                             ": bitmap shorter than range");
+  }
+}
+
 // Range of the pack / unpack bindings: length None = to the end of the
 // device, rounded down to whole granules. Throws when the bitmap does
-// not cover it; the core validates the rest.
+// not cover it.
 uint64_t marked_range(const char* what, Bdev& bdev, uint64_t offset,
                       std::optional<uint64_t> length, uint32_t granule,
                       const std::string& bitmap) {
@@ -148,13 +160,7 @@ uint64_t marked_range(const char* what, Bdev& bdev, uint64_t offset,
   } else if (granule != 0 && offset <= bdev.size_bytes()) {
     len = (bdev.size_bytes() - offset) / granule * granule;
   }
-  if (granule != 0) {
-    const uint64_t n_granules = len / granule;
-    if (bitmap.size() < n_granules / 8 + (n_granules % 8 != 0)) {
-      throw std::runtime_error(std::string(what) +
-                               ": bitmap shorter than range");
-    }
-  }
+  check_bitmap_covers(what, len, granule, bitmap);
   return len;
 }
 
@@ -390,15 +396,8 @@ PYBIND11_MODULE(_hipstore, m) {
     if (length == 0) length = bdev_common_length(src.get(), src_offset, dst.get(),
                                                      dst_offset, granule);
     const std::string raw = bitmap;
-    const uint64_t n_granules = length / granule;
-    if (raw.size() < n_granules / 8 + (n_granules % 8 != 0)) {
-      throw std::runtime_error("bdev_copy_marked: bitmap shorter than range");
-    }
-    std::vector<uint64_t> words((raw.size() + 7) / 8, 0);
-    for (size_t i = 0; i < raw.size(); ++i) {
-      words[i / 8] |= static_cast<uint64_t>(static_cast<uint8_t>(raw[i]))
-                      << (8 * (i % 8));
-    }
+    check_bitmap_covers("bdev_copy_marked", length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
     uint64_t copied = 0;
     int status;
     {
@@ -459,9 +458,15 @@ PYBIND11_MODULE(_hipstore, m) {
     const std::vector<uint64_t> words = bitmap_words(raw);
     const std::string dense = data;
     if (granule != 0) {
+      // Marks below len / granule: whole words, then the masked last one.
+      const uint64_t n_granules = len / granule;
       uint64_t marked = 0;
-      for (uint64_t g = 0; g < len / granule; ++g) {
-        marked += (words[g / 64] >> (g % 64)) & 1;
+      for (uint64_t w = 0; w < n_granules / 64; ++w) {
+        marked += static_cast<uint64_t>(__builtin_popcountll(words[w]));
+      }
+      if (n_granules % 64 != 0) {
+        marked += static_cast<uint64_t>(__builtin_popcountll(
+            words[n_granules / 64] & ((1ull << (n_granules % 64)) - 1)));
       }
       if (dense.size() != marked * granule) {
         throw std::runtime_error(

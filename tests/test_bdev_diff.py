@@ -245,6 +245,28 @@ class TestCopyMarked:
         assert hs.bdev_copy_marked(src, dst, r["bitmap"], BLOCK) == 5
         assert hs.bdev_diff(src, dst)["mismatched"] == 0
 
+    def test_stray_bits_past_the_range(self):
+        """Bits at or past the last granule are neither copied nor
+        counted: inside the last word (70, 71) and in a whole extra word
+        of ones, with marks on both sides of the word boundary."""
+        blocks, n = 192, 70
+        tag = next(_seq)
+        src = hs.create_malloc_bdev(f"stray-s-{tag}", BLOCK, blocks)
+        dst = hs.create_malloc_bdev(f"stray-d-{tag}", BLOCK, blocks)
+        src.fill(0, 0x5A, src.size_bytes)
+        dst.fill(0, 0xC3, dst.size_bytes)
+        marked = [0, 63, 64, 69]
+        bitmap = bytearray(model_bitmap(192, marked + [70, 71]))
+        bitmap[16:24] = b"\xff" * 8
+        copied = hs.bdev_copy_marked(src, dst, bytes(bitmap), BLOCK,
+                                     length=n * BLOCK)
+        assert copied == 4
+        after = dst.read(0, blocks * BLOCK)
+        for g in range(blocks):
+            value = 0x5A if g in marked else 0xC3
+            assert after[g * BLOCK:(g + 1) * BLOCK] == bytes([value]) * BLOCK, \
+                f"granule {g}"
+
     def test_validation(self):
         src, dst = make_pair(64)
         with pytest.raises(RuntimeError):  # bitmap shorter than the range

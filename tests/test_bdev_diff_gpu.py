@@ -197,6 +197,27 @@ class TestCopyMarkedKernel:
         assert c.read((g - 1) * BLOCK, 3 * BLOCK) == want
         assert c.read(marked[1] * BLOCK, BLOCK) == bytes([FILL]) * BLOCK
 
+    def test_stray_bits_past_the_range(self):
+        """Bits at or past the last granule are neither copied nor
+        counted: inside the last word (70, 71) and in a whole extra word
+        of ones, with marks on both sides of the word boundary."""
+        blocks, n = 192, 70
+        src = hs.create_hbm_bdev("dg-stray-s", BLOCK, blocks, device=0)
+        dst = hs.create_hbm_bdev("dg-stray-d", BLOCK, blocks, device=0)
+        src.fill(0, 0x5A, src.size_bytes)
+        dst.fill(0, 0xC3, dst.size_bytes)
+        marked = [0, 63, 64, 69]
+        bitmap = bytearray(model_bitmap(192, marked + [70, 71]))
+        bitmap[16:24] = b"\xff" * 8
+        copied = hs.bdev_copy_marked(src, dst, bytes(bitmap), BLOCK,
+                                     length=n * BLOCK)
+        assert copied == 4
+        after = dst.read(0, blocks * BLOCK)
+        for g in range(blocks):
+            value = 0x5A if g in marked else 0xC3
+            assert after[g * BLOCK:(g + 1) * BLOCK] == bytes([value]) * BLOCK, \
+                f"granule {g}"
+
     def test_coarse_granule_with_offsets(self):
         granule = 4096
         src = hs.create_hbm_bdev("dg-s", BLOCK, 8 * 70, device=0)
