@@ -24,7 +24,7 @@ CORE_OBJS := $(B)/json.o $(B)/bdev.o $(B)/crc32c.o $(B)/rpc_server.o \
              $(B)/methods.o $(B)/nbd.o $(B)/ublk.o $(B)/composite.o $(B)/vhost.o $(B)/vhost_master.o \
              $(B)/nvmf_common.o $(B)/nvmf_target.o $(B)/nvmf_initiator.o \
              $(B)/rados_client.o $(B)/rados_cluster.o $(B)/delta.o \
-             $(B)/gpu.o $(B)/bulk_ops.o
+             $(B)/fingerprint.o $(B)/gpu.o $(B)/bulk_ops.o
 
 .PHONY: all clean
 all: oim_amd/_hipstore$(EXT_SUFFIX) bin/hipstored

@@ -21,6 +21,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "hipstore/bdev.h"
 
@@ -72,5 +73,91 @@ int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
 // Header fields of a file after the structural pass.
 int delta_file_info(const std::string& path, DeltaInfo* info,
                     std::string* error);
+
+// --- fingerprint maps ("hipstore fingerprint map, version 1") ---------------
+//
+// The fingerprints (fingerprint.h) of every granule of a volume, kept in
+// a file next to a checkpoint so that the next incremental checkpoint
+// needs no live clone of its base, and so that a restored volume can be
+// verified, or a volume scrubbed, without a second copy.
+//
+// Layout, little-endian, fully determined by the content:
+//   header, 64 bytes:
+//     "HSFPMAP1", u32 version = 1, u32 block_size, u32 granule,
+//     u32 algorithm = 1, u64 volume_bytes, u64 n_granules, 20 reserved
+//     bytes of 0 (the delta header's n_marked, bitmap_crc and two spare
+//     words), u32 header_crc (CRC32C of bytes 0-59)
+//   records, each the next min(remaining, 65536) fingerprints:
+//     u32 count, u32 crc32c(payload), count * 16 bytes
+//   trailer, 16 bytes: "HSFPEND1", u64 n_granules
+// Reading starts with a structural pass (magic, version, algorithm,
+// header CRC, zero reserved fields, consistent geometry, exact file
+// length, trailer); every record's CRC is then checked before its bytes
+// are used.
+
+constexpr uint32_t kFingerprintMapVersion = 1;
+constexpr uint64_t kFingerprintMapRecord = 65536;  // fingerprints per record
+
+struct FingerprintMapInfo {
+  uint32_t version = 0;
+  uint32_t block_size = 0;
+  uint32_t granule = 0;
+  uint32_t algorithm = 0;
+  uint64_t volume_bytes = 0;
+  uint64_t n_granules = 0;
+  uint64_t file_bytes = 0;
+};
+
+// Writes the fingerprint map of the whole of `bdev` to `path` (tmp file,
+// sync, rename; an existing file is refused without `overwrite`).
+// granule 0 = the block size.
+int bdev_fingerprint_file(Bdev* bdev, const std::string& path,
+                          uint32_t granule, bool overwrite,
+                          FingerprintMapInfo* stats, std::string* error);
+
+// Header fields of a map after the structural pass and every record CRC.
+int fingerprint_map_info(const std::string& path, FingerprintMapInfo* info,
+                         std::string* error);
+
+// Recomputes the fingerprints of `bdev` over the map's range (from
+// offset 0, the map's granule) and compares. Requires equal block size
+// and the map's volume_bytes <= the size of `bdev`. Only reads: allowed
+// on a claimed volume and advisory there, like bdev_diff_sync.
+struct FingerprintVerify {
+  uint32_t granule = 0;
+  uint64_t granules = 0;
+  uint64_t mismatched = 0;
+  // First max_report mismatching granule indices, ascending.
+  std::vector<uint64_t> first_mismatches;
+};
+int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
+                             uint32_t max_report, FingerprintVerify* stats,
+                             std::string* error);
+
+// bdev_export_delta with fingerprint maps. `base_map` names the map of
+// the base state and replaces `base` (giving both is kIoInvalid): one
+// fingerprint pass of `src`, then granule g is exported when it lies at
+// or past the map's n_granules (a grown volume) or its fingerprint
+// differs. The file is a normal version-1 delta (flags 0), byte for byte
+// what a clone of that state as `base` gives, up to the fingerprint's
+// 2^-64 miss probability. granule 0 = the map's granule; any other
+// granule than the map's, another block size or a map larger than `src`
+// is kIoInvalid.
+//
+// `map_out` names where to write the map of `src` as exported: the
+// base_map pass is reused, otherwise a pass of its own runs before the
+// pack. It is renamed into place only after the delta file is, and may
+// name the same file as `base_map` when `overwrite` is set. A write
+// that lands between the fingerprint pass and the pack pass of a claimed
+// volume leaves the new map older than the exported data, so the next
+// delta exports that granule again: the safe direction.
+struct DeltaMaps {
+  std::string base_map;
+  std::string map_out;
+  uint64_t map_bytes = 0;  // out: size of the file written to map_out
+};
+int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
+                      uint32_t granule, bool overwrite, DeltaMaps* maps,
+                      DeltaInfo* stats, std::string* error);
 
 }  // namespace hipstore

@@ -1,7 +1,8 @@
 // GPU data-path engine API. The engines, bdev creation, the pinned
 // helpers, the sync wrappers, IoQueue and bdevperf are implemented in
 // gpu.hip; hbm_copy_sync and the bdev_diff / copy_marked / pack_marked /
-// unpack_marked calls (and marked_copy_probe) in bulk_ops.hip.
+// unpack_marked / fingerprint calls (and marked_copy_probe) in
+// bulk_ops.hip.
 //
 // MI355X-native replacement for the reference's SPDK copy engine +
 // malloc bdev pair (reference lib/copy/copy_engine.c,
@@ -165,6 +166,33 @@ int bdev_unpack_marked_sync(Bdev* dst, uint64_t dst_offset, uint64_t length,
                             uint64_t staging_bytes,
                             const UnpackSource& source,
                             uint64_t* unpacked = nullptr);
+
+// Fingerprints (fingerprint.h, 16 bytes each) of the granules of
+// [offset, +length), handed to `sink` in consecutive windows:
+// sink(fps, first_granule, count) receives `count * 16` bytes for
+// granules first_granule .. first_granule + count - 1 of the range. A
+// non-zero return aborts the call with that status. Every window but the
+// last holds max(1, staging_bytes / 2 / 16) granules (staging_bytes 0 =
+// two halves of 16 MiB, a million granules each).
+//
+// An HBM-resident bdev with a usable GPU runs
+// hipstore::k_fingerprint_granules on its device, one launch per window,
+// writing pinned host memory in place; the callback for one window
+// overlaps the kernel of the next. Every other bdev is read through
+// bdev_read_sync in spans of at most 1 MiB and hashed on the host. Both
+// paths cut the same windows and give the same bytes. The bdev is only
+// read.
+//
+// Validation is that of bdev_diff_sync on the one bdev; also kIoInvalid
+// when 0 < staging_bytes < 32 or the sink is empty. `done` receives the
+// granules delivered.
+using FingerprintSink = std::function<int(const uint8_t* fps,
+                                          uint64_t first_granule,
+                                          uint64_t count)>;
+int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
+                          uint32_t granule, uint64_t staging_bytes,
+                          const FingerprintSink& sink,
+                          uint64_t* done = nullptr);
 
 // Measurement aid for tools/delta_bench.py: moves the marked bytes of
 // an HBM bdev to pinned host memory by plain hipMemcpyAsync (mode 0: one

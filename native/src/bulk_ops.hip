@@ -1,15 +1,17 @@
 // MI355X (gfx950) bulk device operations on HBM bdevs: range copy,
-// CRC32C, granule compare, marked copy and marked pack / unpack. Each
-// call owns its stream, runs to completion and returns; none touches a
-// channel, a ring or a service kernel (those are gpu.hip). Every call
-// but the CRC and the range copy also has a generic path through
-// bdev_read_sync / bdev_write_sync for bdevs that are not HBM-resident.
+// CRC32C, granule compare, marked copy, marked pack / unpack and
+// granule fingerprints. Each call owns its stream, runs to completion
+// and returns; none touches a channel, a ring or a service kernel (those
+// are gpu.hip). Every call but the CRC and the range copy also has a
+// generic path through bdev_read_sync / bdev_write_sync for bdevs that
+// are not HBM-resident.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <numeric>
 #include <stdexcept>
 #include <type_traits>
 #include <vector>
@@ -17,6 +19,7 @@
 #include "gpu_internal.h"
 #include "hipstore/crc32c.h"
 #include "hipstore/engine.h"
+#include "hipstore/fingerprint.h"
 
 namespace hipstore {
 
@@ -244,6 +247,92 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_unpack_marked(
                             rank_before_word, win, granule_bytes);
 }
 
+// --- granule fingerprints (base-less incremental checkpoints) --------------
+//
+// The definition is in fingerprint.h. A wave takes one whole granule at
+// a time and waves grid-stride over granules; lane l is stream l, so its
+// 16-byte loads are vectors l, l + 64, ... and a wave-instruction reads
+// 1 KiB contiguously. Whole rows go four at a time: the four loads are
+// issued before the first dependent round, so several stay in flight
+// behind the two multiply chains. Lanes without a vector keep their
+// seed. The two u64 sums cross the 64 lanes by a shuffle butterfly and
+// lane 0 writes the 16 bytes with one store: no LDS, no atomics, and
+// nothing depends on what `out` held.
+__device__ __forceinline__ uint64_t fp_round(uint64_t acc, uint64_t q) {
+  const uint64_t v = acc + q * kFingerprintP2;
+  return ((v << 31) | (v >> 33)) * kFingerprintP1;
+}
+
+__device__ __forceinline__ uint64_t fp_mix(uint64_t h) {
+  h ^= h >> 33;
+  h *= kFingerprintP2;
+  h ^= h >> 29;
+  h *= kFingerprintP3;
+  h ^= h >> 32;
+  return h;
+}
+
+__device__ __forceinline__ uint64_t fp_q0(const uint4 v) {
+  return (static_cast<uint64_t>(v.y) << 32) | v.x;
+}
+__device__ __forceinline__ uint64_t fp_q1(const uint4 v) {
+  return (static_cast<uint64_t>(v.w) << 32) | v.z;
+}
+
+constexpr uint32_t kFingerprintUnroll = 4;  // rows loaded ahead of their rounds
+
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_fingerprint_granules(
+    const uint8_t* __restrict__ base, uint64_t n_granules,
+    uint32_t granule_bytes, uint4* __restrict__ out) {
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule_bytes >> 4;
+  const uint32_t rows = n16 >> 6;  // whole rows of 64 vectors
+  const uint32_t rest = n16 & 63;  // vectors of the ragged last row
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kWavesPerWg;
+  for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kWavesPerWg + wave;
+       g < n_granules; g += stride) {  // wave-uniform
+    const uint4* __restrict__ p =
+        reinterpret_cast<const uint4*>(base + g * granule_bytes) + lane;
+    uint64_t a = kFingerprintP1 * (lane + 1);
+    uint64_t b = kFingerprintP2 * (lane + 1);
+    uint32_t r = 0;
+    for (; r + kFingerprintUnroll <= rows; r += kFingerprintUnroll) {
+      uint4 v[kFingerprintUnroll];
+#pragma unroll
+      for (uint32_t k = 0; k < kFingerprintUnroll; ++k) v[k] = p[(r + k) * 64];
+#pragma unroll
+      for (uint32_t k = 0; k < kFingerprintUnroll; ++k) {
+        a = fp_round(a, fp_q0(v[k]));
+        b = fp_round(b, fp_q1(v[k]));
+      }
+    }
+    for (; r < rows; ++r) {
+      const uint4 v = p[r * 64];
+      a = fp_round(a, fp_q0(v));
+      b = fp_round(b, fp_q1(v));
+    }
+    if (lane < rest) {
+      const uint4 v = p[rows * 64];
+      a = fp_round(a, fp_q0(v));
+      b = fp_round(b, fp_q1(v));
+    }
+    uint64_t d0 = fp_mix(a ^ fp_mix(b));
+    uint64_t d1 = fp_mix(b + fp_mix(a));
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+      d0 += __shfl_xor(d0, m);
+      d1 += __shfl_xor(d1, m);
+    }
+    if (lane == 0) {
+      out[g] = make_uint4(static_cast<uint32_t>(d0),
+                          static_cast<uint32_t>(d0 >> 32),
+                          static_cast<uint32_t>(d1),
+                          static_cast<uint32_t>(d1 >> 32));
+    }
+  }
+}
+
 // --- host helpers shared by every call below -------------------------------
 
 // A one-shot stream: device selected, own non-blocking stream created
@@ -310,6 +399,7 @@ struct BulkCtx {
   PinnedBuf<uint32_t> ranks;    // exclusive prefix popcount of `words`
   PinnedBuf<uint8_t> chunks;    // 2 x kDiffHostChunk, generic compare / copy
   PinnedBuf<uint8_t> staging;   // dense stream (two halves on the GPU path)
+  PinnedBuf<uint8_t> prints;    // fingerprints (two halves on the GPU path)
 };
 constexpr uint64_t kMinBitmapWords = 4096;  // floor of `words` and `ranks`
 
@@ -781,6 +871,25 @@ void wait_marked_event(hipEvent_t event) {
   HIP_CHECK(err);
 }
 
+// A one-shot stream with one event per half of a two-half pinned
+// buffer: the window loops below launch into one half while the host
+// works on the other.
+struct HalvesStream : ScopedStream {
+  hipEvent_t done[2] = {nullptr, nullptr};
+
+  explicit HalvesStream(int device) : ScopedStream(device) {
+    for (hipEvent_t& e : done) {
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+  }
+  ~HalvesStream() {
+    (void)hipStreamSynchronize(stream);  // before the events go
+    for (hipEvent_t e : done) {
+      if (e != nullptr) (void)hipEventDestroy(e);
+    }
+  }
+};
+
 uint32_t marked_window_grid(const MarkedWindow& win) {
   return granule_grid((win.g_end + 63) / 64 * 64 - win.g_begin / 64 * 64);
 }
@@ -789,8 +898,7 @@ uint32_t marked_window_grid(const MarkedWindow& win) {
 // staging half: launch window k+1, then wait for window k only. The
 // kernels read the plan and fill or drain the two halves in place, so
 // the device's view of those is kept here too.
-struct MarkedStream : ScopedStream {
-  hipEvent_t done[2] = {nullptr, nullptr};
+struct MarkedStream : HalvesStream {
   uint32_t granule;
   uint64_t half_bytes;
   uint8_t* staging;
@@ -801,22 +909,12 @@ struct MarkedStream : ScopedStream {
 
   MarkedStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
                const MarkedPlan& plan)
-      : ScopedStream(device), granule(granule_bytes),
+      : HalvesStream(device), granule(granule_bytes),
         half_bytes(plan.chunk_granules * granule_bytes),
         staging(bulk_ctx().staging.reserve(2 * half_bytes)),
         dev_staging(device_view(staging)), dev_words(device_view(plan.words)),
         dev_ranks(device_view(plan.ranks)),
-        base(static_cast<uint8_t*>(bdev->device_base()) + offset) {
-    for (hipEvent_t& e : done) {
-      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-  }
-  ~MarkedStream() {
-    (void)hipStreamSynchronize(stream);  // before the events go
-    for (hipEvent_t e : done) {
-      if (e != nullptr) (void)hipEventDestroy(e);
-    }
-  }
+        base(static_cast<uint8_t*>(bdev->device_base()) + offset) {}
 
   // k_pack_marked or k_unpack_marked over one window and one half.
   template <typename Kernel>
@@ -974,6 +1072,123 @@ int bdev_unpack_marked_sync(Bdev* dst, uint64_t dst_offset, uint64_t length,
                             const UnpackSource& source, uint64_t* unpacked) {
   return marked_stream_sync(dst, dst_offset, length, granule, bitmap,
                             staging_bytes, source, unpacked);
+}
+
+// ---------------------------------------------------------------------------
+// Granule fingerprints
+// ---------------------------------------------------------------------------
+
+namespace {
+
+uint32_t fingerprint_grid(uint64_t n_granules) {
+  return static_cast<uint32_t>(std::min<uint64_t>(
+      (n_granules + kWavesPerWg - 1) / kWavesPerWg, 2048));
+}
+
+// One launch per window of `window` granules, fingerprints written in
+// place into one half of `prints`; window k+1 runs while the sink sees
+// window k.
+int fingerprint_gpu(int device, Bdev* bdev, uint64_t offset,
+                    uint64_t n_granules, uint32_t granule, uint64_t window,
+                    const FingerprintSink& sink, uint64_t* done) {
+  HalvesStream hs(device);
+  const uint64_t half_bytes = window * kFingerprintBytes;
+  uint8_t* prints = bulk_ctx().prints.reserve(2 * half_bytes);
+  uint8_t* dev_prints = device_view(prints);
+  const uint8_t* base = static_cast<uint8_t*>(bdev->device_base()) + offset;
+  auto launch = [&](uint64_t first, int half) {
+    const uint64_t count = std::min(window, n_granules - first);  // >= 1
+    hipLaunchKernelGGL(k_fingerprint_granules, dim3(fingerprint_grid(count)),
+                       dim3(kWavesPerWg * 64), 0, hs.stream,
+                       base + first * granule, count, granule,
+                       reinterpret_cast<uint4*>(dev_prints + half * half_bytes));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(hs.done[half], hs.stream));
+  };
+  launch(0, 0);
+  for (int half = 0;; half ^= 1) {
+    const uint64_t first = *done;
+    const uint64_t count = std::min(window, n_granules - first);
+    if (first + count < n_granules) launch(first + count, half ^ 1);
+    wait_marked_event(hs.done[half]);
+    const int status = sink(prints + half * half_bytes, first, count);
+    if (status != 0) return status;
+    *done = first + count;
+    if (*done >= n_granules) return kIoOk;
+  }
+}
+
+// Generic path: the same windows, read in spans of at most 1 MiB through
+// the incremental hasher (a granule may be larger than a span).
+int fingerprint_generic(Bdev* bdev, uint64_t offset, uint64_t n_granules,
+                        uint32_t granule, uint64_t window,
+                        const FingerprintSink& sink, uint64_t* done) {
+  // Spans are cut on multiples of the block size and of 16.
+  const uint64_t unit = std::lcm<uint64_t>(bdev->block_size(), 16);
+  const uint64_t span = kDiffHostChunk / unit * unit;
+  if (span == 0) return kIoInvalid;
+  uint8_t* prints = bulk_ctx().prints.reserve(window * kFingerprintBytes);
+  uint8_t* buf = bulk_ctx().chunks.reserve(2 * kDiffHostChunk);
+  GranuleHasher hasher;
+  while (*done < n_granules) {
+    const uint64_t first = *done;
+    const uint64_t count = std::min(window, n_granules - first);
+    const uint64_t bytes = count * granule;
+    uint64_t in_granule = 0;  // bytes of the current granule hashed so far
+    uint64_t filled = 0;      // granules of this window finished
+    for (uint64_t pos = 0; pos < bytes; pos += span) {
+      const uint64_t n = std::min(span, bytes - pos);
+      const int status =
+          bdev_read_sync(bdev, offset + first * granule + pos, buf, n);
+      if (status != kIoOk) return status;
+      for (uint64_t off = 0; off < n;) {
+        const uint64_t piece = std::min<uint64_t>(granule - in_granule, n - off);
+        hasher.update(buf + off, piece);
+        off += piece;
+        in_granule += piece;
+        if (in_granule == granule) {
+          hasher.finish(prints + filled * kFingerprintBytes);
+          ++filled;
+          in_granule = 0;
+        }
+      }
+    }
+    const int status = sink(prints, first, count);
+    if (status != 0) return status;
+    *done = first + count;
+  }
+  return kIoOk;
+}
+
+}  // namespace
+
+int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
+                          uint32_t granule, uint64_t staging_bytes,
+                          const FingerprintSink& sink, uint64_t* done_out) {
+  uint64_t unused = 0;
+  uint64_t* done = done_out != nullptr ? done_out : &unused;
+  *done = 0;
+  try {
+    if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule) ||
+        (staging_bytes != 0 && staging_bytes < 2 * kFingerprintBytes) ||
+        !sink) {
+      return kIoInvalid;
+    }
+    const uint64_t n_granules = length / granule;  // >= 1
+    const uint64_t half =
+        staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
+    const uint64_t window =
+        std::min(std::max<uint64_t>(1, half / kFingerprintBytes), n_granules);
+    const int device = granule_kernel_device(bdev, bdev);
+    if (device >= 0) {
+      return fingerprint_gpu(device, bdev, offset, n_granules, granule, window,
+                             sink, done);
+    }
+    return fingerprint_generic(bdev, offset, n_granules, granule, window, sink,
+                               done);
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
 }
 
 // Measurement aid (tools/delta_bench.py): times, on the host clock from

@@ -1,4 +1,5 @@
-// hipstore delta files: export / import of marked granules (delta.h).
+// hipstore delta files: export / import of marked granules, and
+// fingerprint maps (delta.h).
 
 #include "hipstore/delta.h"
 
@@ -13,6 +14,7 @@
 
 #include "hipstore/crc32c.h"
 #include "hipstore/engine.h"
+#include "hipstore/fingerprint.h"
 
 namespace hipstore {
 
@@ -310,34 +312,268 @@ class RecordReader {
   std::vector<uint8_t> buf_;
 };
 
+// --- fingerprint maps --------------------------------------------------------
+
+const char kMapMagic[8] = {'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'};
+const char kMapEndMagic[8] = {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'};
+
+struct LoadedMap {
+  FingerprintMapInfo info;
+  std::vector<uint8_t> fps;  // n_granules * 16 bytes
+};
+
+// Structural pass, then every record with its CRC checked before its
+// bytes are kept.
+int load_map(const std::string& path, LoadedMap* out, std::string* error) {
+  Fd in;
+  in.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  if (in.fd < 0) return fail(error, kIoFailed, errno_text("open " + path));
+  struct stat st;
+  if (fstat(in.fd, &st) != 0) {
+    return fail(error, kIoFailed, errno_text("fstat"));
+  }
+  if (!S_ISREG(st.st_mode)) {
+    return fail(error, kIoInvalid, "not a regular file");
+  }
+  const uint64_t file_bytes = static_cast<uint64_t>(st.st_size);
+  uint8_t h[kDeltaHeaderBytes];
+  if (file_bytes < kDeltaHeaderBytes + kDeltaTrailerBytes ||
+      !read_all(in.fd, h, sizeof(h), 0)) {
+    return fail(error, kIoInvalid, "file shorter than header and trailer");
+  }
+  if (memcmp(h, kMapMagic, 8) != 0) {
+    return fail(error, kIoInvalid,
+                "not a hipstore fingerprint map (bad magic)");
+  }
+  if (get_u32(h + 60) != crc32c_sw(0, h, 60)) {
+    return fail(error, kIoInvalid, "header CRC mismatch");
+  }
+  FingerprintMapInfo& info = out->info;
+  info.version = get_u32(h + 8);
+  info.block_size = get_u32(h + 12);
+  info.granule = get_u32(h + 16);
+  info.algorithm = get_u32(h + 20);
+  info.volume_bytes = get_u64(h + 24);
+  info.n_granules = get_u64(h + 32);
+  info.file_bytes = file_bytes;
+  if (info.version != kFingerprintMapVersion) {
+    return fail(error, kIoInvalid, "unsupported fingerprint map version");
+  }
+  if (info.algorithm != kFingerprintAlgorithm) {
+    return fail(error, kIoInvalid, "unknown fingerprint algorithm");
+  }
+  for (int at = 40; at < 60; ++at) {
+    if (h[at] != 0) {
+      return fail(error, kIoInvalid, "non-zero reserved field");
+    }
+  }
+  if (info.block_size == 0 || info.granule == 0 ||
+      info.granule % info.block_size != 0 || info.granule % 16 != 0 ||
+      info.n_granules == 0 || info.n_granules > kMaxGranules ||
+      info.volume_bytes / info.granule != info.n_granules ||
+      info.volume_bytes % info.granule != 0) {
+    return fail(error, kIoInvalid, "inconsistent geometry in header");
+  }
+  // n_granules <= 2^31: no sum wraps.
+  const uint64_t n_records =
+      (info.n_granules + kFingerprintMapRecord - 1) / kFingerprintMapRecord;
+  const uint64_t expected = kDeltaHeaderBytes + n_records * 8 +
+                            info.n_granules * kFingerprintBytes +
+                            kDeltaTrailerBytes;
+  if (file_bytes != expected) {
+    return fail(error, kIoInvalid,
+                "file length " + std::to_string(file_bytes) +
+                    " does not follow from the header (" +
+                    std::to_string(expected) + ")");
+  }
+  uint8_t t[kDeltaTrailerBytes];
+  if (!read_all(in.fd, t, sizeof(t), file_bytes - kDeltaTrailerBytes)) {
+    return fail(error, kIoFailed, "cannot read trailer");
+  }
+  if (memcmp(t, kMapEndMagic, 8) != 0 || get_u64(t + 8) != info.n_granules) {
+    return fail(error, kIoInvalid, "bad trailer");
+  }
+  out->fps.resize(info.n_granules * kFingerprintBytes);
+  uint64_t offset = kDeltaHeaderBytes;
+  for (uint64_t first = 0, index = 0; first < info.n_granules; ++index) {
+    const uint64_t want =
+        std::min(kFingerprintMapRecord, info.n_granules - first);
+    uint8_t head[8];
+    uint8_t* payload = &out->fps[first * kFingerprintBytes];
+    if (!read_all(in.fd, head, 8, offset) ||
+        !read_all(in.fd, payload, want * kFingerprintBytes, offset + 8)) {
+      return fail(error, kIoFailed, "cannot read record");
+    }
+    if (get_u32(head) != want) {
+      return fail(error, kIoInvalid,
+                  "record " + std::to_string(index) + " has a wrong count");
+    }
+    if (crc32c_sw(0, payload, want * kFingerprintBytes) != get_u32(head + 4)) {
+      return fail(error, kIoInvalid,
+                  "record " + std::to_string(index) + " CRC mismatch");
+    }
+    offset += 8 + want * kFingerprintBytes;
+    first += want;
+  }
+  return kIoOk;
+}
+
+// Writes a complete, synced map to `tmp`; the caller renames it.
+int write_map_tmp(const std::string& tmp, uint32_t block_size,
+                  uint32_t granule, const std::vector<uint8_t>& fps,
+                  uint64_t* file_bytes, std::string* error) {
+  const uint64_t n_granules = fps.size() / kFingerprintBytes;
+  Fd out;
+  out.fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+  if (out.fd < 0) return fail(error, kIoFailed, errno_text("open " + tmp));
+  uint8_t h[kDeltaHeaderBytes] = {0};
+  memcpy(h, kMapMagic, 8);
+  put_u32(h + 8, kFingerprintMapVersion);
+  put_u32(h + 12, block_size);
+  put_u32(h + 16, granule);
+  put_u32(h + 20, kFingerprintAlgorithm);
+  put_u64(h + 24, n_granules * granule);
+  put_u64(h + 32, n_granules);
+  put_u32(h + 60, crc32c_sw(0, h, 60));
+  bool ok = write_all(out.fd, h, sizeof(h));
+  uint64_t bytes = sizeof(h);
+  for (uint64_t first = 0; ok && first < n_granules;) {
+    const uint64_t count =
+        std::min(kFingerprintMapRecord, n_granules - first);
+    const uint8_t* payload = &fps[first * kFingerprintBytes];
+    uint8_t head[8];
+    put_u32(head, static_cast<uint32_t>(count));
+    put_u32(head + 4, crc32c_sw(0, payload, count * kFingerprintBytes));
+    ok = write_all(out.fd, head, 8) &&
+         write_all(out.fd, payload, count * kFingerprintBytes);
+    bytes += 8 + count * kFingerprintBytes;
+    first += count;
+  }
+  uint8_t t[kDeltaTrailerBytes];
+  memcpy(t, kMapEndMagic, 8);
+  put_u64(t + 8, n_granules);
+  bytes += sizeof(t);
+  if (!ok || !write_all(out.fd, t, sizeof(t)) || fsync(out.fd) != 0) {
+    const std::string why = errno_text("write " + tmp);
+    unlink(tmp.c_str());
+    return fail(error, kIoFailed, why);
+  }
+  *file_bytes = bytes;
+  return kIoOk;
+}
+
+// One fingerprint pass over [0, length) of `bdev`. With `stored`, bit g
+// of `bitmap` is set when granule g has no stored fingerprint or differs
+// from it; with `keep`, the fingerprints are kept.
+int fingerprint_pass(Bdev* bdev, uint64_t length, uint32_t granule,
+                     const std::vector<uint8_t>* stored,
+                     std::vector<uint64_t>* bitmap,
+                     std::vector<uint8_t>* keep) {
+  if (granule == 0 || length % granule != 0) return kIoInvalid;
+  const uint64_t n_granules = length / granule;
+  if (n_granules > kMaxGranules) return kIoInvalid;
+  if (bitmap != nullptr) bitmap->assign((n_granules + 63) / 64, 0);
+  if (keep != nullptr) keep->resize(n_granules * kFingerprintBytes);
+  const uint64_t n_stored =
+      stored != nullptr ? stored->size() / kFingerprintBytes : 0;
+  uint64_t done = 0;
+  const int status = bdev_fingerprint_sync(
+      bdev, 0, length, granule, 0,
+      [&](const uint8_t* fps, uint64_t first, uint64_t count) {
+        if (keep != nullptr) {
+          memcpy(&(*keep)[first * kFingerprintBytes], fps,
+                 count * kFingerprintBytes);
+        }
+        if (bitmap != nullptr) {
+          for (uint64_t i = 0; i < count; ++i) {
+            const uint64_t g = first + i;
+            if (g >= n_stored ||
+                memcmp(fps + i * kFingerprintBytes,
+                       &(*stored)[g * kFingerprintBytes],
+                       kFingerprintBytes) != 0) {
+              (*bitmap)[g / 64] |= 1ull << (g % 64);
+            }
+          }
+        }
+        return 0;
+      },
+      &done);
+  if (status == kIoOk && done != n_granules) return kIoFailed;
+  return status;
+}
+
+const char kBadGranule[] =
+    "invalid granule (a multiple of the block size and of 16 that divides "
+    "the volume size)";
+
 }  // namespace
 
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaInfo* stats,
                       std::string* error) {
+  return bdev_export_delta(src, base, path, granule, overwrite, nullptr, stats,
+                           error);
+}
+
+int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
+                      uint32_t granule, bool overwrite, DeltaMaps* maps,
+                      DeltaInfo* stats, std::string* error) {
   if (src == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
   }
-  if (granule == 0) granule = static_cast<uint32_t>(src->block_size());
+  const std::string base_map = maps != nullptr ? maps->base_map : "";
+  const std::string map_out = maps != nullptr ? maps->map_out : "";
+  if (maps != nullptr) maps->map_bytes = 0;
+  if (base != nullptr && !base_map.empty()) {
+    return fail(error, kIoInvalid, "base and base_map exclude each other");
+  }
+  if (map_out == path) {
+    return fail(error, kIoInvalid, "map_out names the delta file");
+  }
   const uint64_t length = src->size_bytes();
   if (src->block_size() > UINT32_MAX) {
     return fail(error, kIoInvalid, "block size too large");
   }
+  LoadedMap stored;
+  if (!base_map.empty()) {
+    const int status = load_map(base_map, &stored, error);
+    if (status != kIoOk) return status;
+    if (granule != 0 && granule != stored.info.granule) {
+      return fail(error, kIoInvalid,
+                  "granule differs from the base map's (" +
+                      std::to_string(stored.info.granule) + ")");
+    }
+    granule = stored.info.granule;
+    if (stored.info.block_size != src->block_size() ||
+        stored.info.volume_bytes > length) {
+      return fail(error, kIoInvalid,
+                  "base map has another block size or a larger volume");
+    }
+  }
+  if (granule == 0) granule = static_cast<uint32_t>(src->block_size());
   if (base != nullptr && (base->block_size() != src->block_size() ||
                           base->size_bytes() != length)) {
     return fail(error, kIoInvalid,
                 "base and volume differ in block size or size");
   }
   std::vector<uint64_t> bitmap;
+  std::vector<uint8_t> fps;  // of src, when map_out asks for them
   uint64_t n_marked = 0;
-  if (base != nullptr) {
+  if (!base_map.empty()) {
+    const int status =
+        fingerprint_pass(src, length, granule, &stored.fps, &bitmap,
+                         map_out.empty() ? nullptr : &fps);
+    if (status == kIoInvalid) return fail(error, kIoInvalid, kBadGranule);
+    if (status != kIoOk) return fail(error, kIoFailed, "fingerprint pass failed");
+    for (uint64_t word : bitmap) {
+      n_marked += static_cast<uint64_t>(__builtin_popcountll(word));
+    }
+  } else if (base != nullptr) {
     DiffStats diff;
     const int status =
         bdev_diff_sync(base, 0, src, 0, length, granule, 0, &bitmap, &diff);
     if (status == kIoInvalid) {
-      return fail(error, kIoInvalid,
-                  "invalid granule (a multiple of the block size and of 16 "
-                  "that divides the volume size)");
+      return fail(error, kIoInvalid, kBadGranule);
     }
     if (status != kIoOk) return fail(error, kIoFailed, "compare failed");
     n_marked = diff.mismatched;
@@ -345,21 +581,31 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
     if (granule % 16 != 0 || granule % src->block_size() != 0 ||
         length == 0 || length % granule != 0 ||
         length / granule > kMaxGranules) {
-      return fail(error, kIoInvalid,
-                  "invalid granule (a multiple of the block size and of 16 "
-                  "that divides the volume size)");
+      return fail(error, kIoInvalid, kBadGranule);
     }
     n_marked = length / granule;
     bitmap.assign((n_marked + 63) / 64, ~0ull);
     if (n_marked % 64 != 0) bitmap.back() = (1ull << (n_marked % 64)) - 1;
   }
   const uint64_t n_granules = length / granule;
+  const bool full = base == nullptr && base_map.empty();
 
   struct stat st;
   if (!overwrite && lstat(path.c_str(), &st) == 0) {
     return fail(error, kIoFailed, path + " exists (overwrite not set)");
   }
+  if (!overwrite && !map_out.empty() && lstat(map_out.c_str(), &st) == 0) {
+    return fail(error, kIoFailed, map_out + " exists (overwrite not set)");
+  }
+  // The map is taken before the pack pass: a write in between leaves it
+  // older than the exported data, never newer.
+  if (!map_out.empty() && base_map.empty()) {
+    const int status =
+        fingerprint_pass(src, length, granule, nullptr, nullptr, &fps);
+    if (status != kIoOk) return fail(error, kIoFailed, "fingerprint pass failed");
+  }
   const std::string tmp = path + ".tmp";
+  const std::string map_tmp = map_out + ".tmp";
   Fd out;
   out.fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
   if (out.fd < 0) return fail(error, kIoFailed, errno_text("open " + tmp));
@@ -370,7 +616,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   put_u32(h + 8, kDeltaVersion);
   put_u32(h + 12, static_cast<uint32_t>(src->block_size()));
   put_u32(h + 16, granule);
-  put_u32(h + 20, base == nullptr ? kDeltaFlagFull : 0);
+  put_u32(h + 20, full ? kDeltaFlagFull : 0);
   put_u64(h + 24, length);
   put_u64(h + 32, n_granules);
   put_u64(h + 40, n_marked);
@@ -410,19 +656,35 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
       why = errno_text("write " + tmp);
     }
   }
+  // Both files are complete under their .tmp names before either
+  // appears; the map follows the delta it belongs to.
+  uint64_t map_bytes = 0;
+  bool map_written = false;
+  if (status == kIoOk && !map_out.empty()) {
+    status = write_map_tmp(map_tmp, static_cast<uint32_t>(src->block_size()),
+                           granule, fps, &map_bytes, &why);
+    map_written = status == kIoOk;
+  }
   if (status == kIoOk && rename(tmp.c_str(), path.c_str()) != 0) {
     status = kIoFailed;
     why = errno_text("rename to " + path);
   }
   if (status != kIoOk) {
     unlink(tmp.c_str());
+    if (map_written) unlink(map_tmp.c_str());
     return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed, why);
   }
+  if (map_written && rename(map_tmp.c_str(), map_out.c_str()) != 0) {
+    why = errno_text("rename to " + map_out);
+    unlink(map_tmp.c_str());
+    return fail(error, kIoFailed, why + " (" + path + " was written)");
+  }
+  if (maps != nullptr) maps->map_bytes = map_bytes;
   if (stats != nullptr) {
     stats->version = kDeltaVersion;
     stats->block_size = static_cast<uint32_t>(src->block_size());
     stats->granule = granule;
-    stats->full = base == nullptr;
+    stats->full = full;
     stats->volume_bytes = length;
     stats->n_granules = n_granules;
     stats->n_marked = n_marked;
@@ -440,6 +702,97 @@ int delta_file_info(const std::string& path, DeltaInfo* info,
   const int status = parse_file(in.fd, &file, error);
   if (status == kIoOk && info != nullptr) *info = file.info;
   return status;
+}
+
+int bdev_fingerprint_file(Bdev* bdev, const std::string& path,
+                          uint32_t granule, bool overwrite,
+                          FingerprintMapInfo* stats, std::string* error) {
+  if (bdev == nullptr || path.empty()) {
+    return fail(error, kIoInvalid, "bdev and path required");
+  }
+  if (bdev->block_size() > UINT32_MAX) {
+    return fail(error, kIoInvalid, "block size too large");
+  }
+  if (granule == 0) granule = static_cast<uint32_t>(bdev->block_size());
+  const uint64_t length = bdev->size_bytes();
+  struct stat st;
+  if (!overwrite && lstat(path.c_str(), &st) == 0) {
+    return fail(error, kIoFailed, path + " exists (overwrite not set)");
+  }
+  std::vector<uint8_t> fps;
+  int status = fingerprint_pass(bdev, length, granule, nullptr, nullptr, &fps);
+  if (status == kIoInvalid) return fail(error, kIoInvalid, kBadGranule);
+  if (status != kIoOk) return fail(error, kIoFailed, "fingerprint pass failed");
+  const std::string tmp = path + ".tmp";
+  uint64_t file_bytes = 0;
+  status = write_map_tmp(tmp, static_cast<uint32_t>(bdev->block_size()),
+                         granule, fps, &file_bytes, error);
+  if (status != kIoOk) return status;
+  if (rename(tmp.c_str(), path.c_str()) != 0) {
+    const std::string why = errno_text("rename to " + path);
+    unlink(tmp.c_str());
+    return fail(error, kIoFailed, why);
+  }
+  if (stats != nullptr) {
+    stats->version = kFingerprintMapVersion;
+    stats->block_size = static_cast<uint32_t>(bdev->block_size());
+    stats->granule = granule;
+    stats->algorithm = kFingerprintAlgorithm;
+    stats->volume_bytes = length;
+    stats->n_granules = length / granule;
+    stats->file_bytes = file_bytes;
+  }
+  return kIoOk;
+}
+
+int fingerprint_map_info(const std::string& path, FingerprintMapInfo* info,
+                         std::string* error) {
+  LoadedMap map;
+  const int status = load_map(path, &map, error);
+  if (status == kIoOk && info != nullptr) *info = map.info;
+  return status;
+}
+
+int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
+                             uint32_t max_report, FingerprintVerify* stats,
+                             std::string* error) {
+  if (bdev == nullptr || path.empty()) {
+    return fail(error, kIoInvalid, "bdev and path required");
+  }
+  LoadedMap map;
+  int status = load_map(path, &map, error);
+  if (status != kIoOk) return status;
+  if (map.info.block_size != bdev->block_size()) {
+    return fail(error, kIoInvalid,
+                "map block size " + std::to_string(map.info.block_size) +
+                    " differs from the volume's");
+  }
+  if (map.info.volume_bytes > bdev->size_bytes()) {
+    return fail(error, kIoInvalid, "map volume is larger than the bdev");
+  }
+  std::vector<uint64_t> bitmap;
+  status = fingerprint_pass(bdev, map.info.volume_bytes, map.info.granule,
+                            &map.fps, &bitmap, nullptr);
+  if (status != kIoOk) {
+    return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
+                "fingerprint pass failed");
+  }
+  if (stats != nullptr) {
+    stats->granule = map.info.granule;
+    stats->granules = map.info.n_granules;
+    stats->mismatched = 0;
+    stats->first_mismatches.clear();
+    for (uint64_t w = 0; w < bitmap.size(); ++w) {
+      uint64_t word = bitmap[w];
+      stats->mismatched += static_cast<uint64_t>(__builtin_popcountll(word));
+      while (word != 0 && stats->first_mismatches.size() < max_report) {
+        stats->first_mismatches.push_back(
+            w * 64 + static_cast<uint64_t>(__builtin_ctzll(word)));
+        word &= word - 1;
+      }
+    }
+  }
+  return kIoOk;
 }
 
 int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,

@@ -1102,12 +1102,23 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         }
         const std::string path = p.get_string("path");
         if (path.empty()) throw RpcError{kInvalidParams, "path required"};
-        const uint32_t granule = granule_param(p, src);
+        DeltaMaps maps;
+        if (p.has("base_map")) maps.base_map = p.get_string("base_map");
+        if (p.has("map_out")) maps.map_out = p.get_string("map_out");
+        if ((p.has("base_map") && maps.base_map.empty()) ||
+            (p.has("map_out") && maps.map_out.empty())) {
+          throw RpcError{kInvalidParams, "base_map / map_out must not be empty"};
+        }
+        // With base_map, an absent granule means the map's.
+        const uint32_t granule =
+            !maps.base_map.empty() && !p.has("granule") ? 0
+                                                        : granule_param(p, src);
         DeltaInfo info;
         std::string why;
         const int status =
             bdev_export_delta(src.get(), base.get(), path, granule,
-                              p.get_bool("overwrite", false), &info, &why);
+                              p.get_bool("overwrite", false), &maps, &info,
+                              &why);
         if (status != kIoOk) throw delta_error("bdev_export_delta", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));
@@ -1115,6 +1126,57 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         o["saved"] = Json(static_cast<int64_t>(info.n_marked));
         o["file_bytes"] = Json(static_cast<int64_t>(info.file_bytes));
         o["full"] = Json(info.full);
+        if (!maps.map_out.empty()) {
+          o["map_bytes"] = Json(static_cast<int64_t>(maps.map_bytes));
+        }
+        return Json(std::move(o));
+      });
+
+  server->register_method(
+      "bdev_fingerprint", [&manager, granule_param, delta_error](const Json& p) {
+        // Writes the fingerprint map of a volume (HBM volumes are hashed
+        // by k_fingerprint_granules, 16 bytes per granule leave the GPU).
+        const std::string name = p.get_string("name");
+        BdevPtr bdev = manager.find(name);
+        if (!bdev) not_found("bdev " + name);
+        const std::string path = p.get_string("path");
+        if (path.empty()) throw RpcError{kInvalidParams, "path required"};
+        FingerprintMapInfo info;
+        std::string why;
+        const int status = bdev_fingerprint_file(
+            bdev.get(), path, granule_param(p, bdev),
+            p.get_bool("overwrite", false), &info, &why);
+        if (status != kIoOk) throw delta_error("bdev_fingerprint", status, why);
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(info.granule));
+        o["granules"] = Json(static_cast<int64_t>(info.n_granules));
+        o["map_bytes"] = Json(static_cast<int64_t>(info.file_bytes));
+        return Json(std::move(o));
+      });
+
+  server->register_method(
+      "bdev_verify_fingerprints",
+      [&manager, max_report_param, indices_to_json,
+       delta_error](const Json& p) {
+        // Recomputes a volume's fingerprints over a map's range and
+        // compares; read-only, so a claimed volume is allowed (advisory).
+        const std::string name = p.get_string("name");
+        BdevPtr bdev = manager.find(name);
+        if (!bdev) not_found("bdev " + name);
+        const std::string path = p.get_string("path");
+        if (path.empty()) throw RpcError{kInvalidParams, "path required"};
+        FingerprintVerify r;
+        std::string why;
+        const int status = bdev_verify_fingerprints(
+            bdev.get(), path, max_report_param(p), &r, &why);
+        if (status != kIoOk) {
+          throw delta_error("bdev_verify_fingerprints", status, why);
+        }
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(r.granule));
+        o["granules"] = Json(static_cast<int64_t>(r.granules));
+        o["mismatched"] = Json(static_cast<int64_t>(r.mismatched));
+        o["first_mismatches"] = indices_to_json(r.first_mismatches);
         return Json(std::move(o));
       });
 

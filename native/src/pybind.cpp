@@ -18,6 +18,7 @@
 #include "hipstore/crc32c.h"
 #include "hipstore/delta.h"
 #include "hipstore/engine.h"
+#include "hipstore/fingerprint.h"
 #include "hipstore/nvmf.h"
 #include "hipstore/rados.h"
 #include "hipstore/vhost_master.h"
@@ -173,6 +174,18 @@ py::dict delta_info_to_dict(const DeltaInfo& info) {
   d["volume_bytes"] = info.volume_bytes;
   d["granules"] = info.n_granules;
   d["marked"] = info.n_marked;
+  d["file_bytes"] = info.file_bytes;
+  return d;
+}
+
+py::dict map_info_to_dict(const FingerprintMapInfo& info) {
+  py::dict d;
+  d["version"] = info.version;
+  d["block_size"] = info.block_size;
+  d["granule"] = info.granule;
+  d["algorithm"] = info.algorithm;
+  d["volume_bytes"] = info.volume_bytes;
+  d["granules"] = info.n_granules;
   d["file_bytes"] = info.file_bytes;
   return d;
 }
@@ -527,22 +540,32 @@ PYBIND11_MODULE(_hipstore, m) {
   m.def("bdev_export_delta", [](BdevPtr src, const std::string& path,
                                 std::optional<BdevPtr> base,
                                 std::optional<uint32_t> granule,
-                                bool overwrite) {
+                                bool overwrite,
+                                std::optional<std::string> base_map,
+                                std::optional<std::string> map_out) {
     DeltaInfo info;
+    DeltaMaps maps;
+    maps.base_map = base_map.value_or("");
+    maps.map_out = map_out.value_or("");
     std::string error;
     int status;
     {
       py::gil_scoped_release release;
       status = bdev_export_delta(src.get(), base ? base->get() : nullptr,
-                                 path, granule.value_or(0), overwrite, &info,
-                                 &error);
+                                 path, granule.value_or(0), overwrite, &maps,
+                                 &info, &error);
     }
     if (status != kIoOk) throw_delta("bdev_export_delta", status, error);
-    return delta_info_to_dict(info);
+    py::dict d = delta_info_to_dict(info);
+    if (!maps.map_out.empty()) d["map_bytes"] = maps.map_bytes;
+    return d;
   }, py::arg("src"), py::arg("path"), py::arg("base") = py::none(),
      py::arg("granule") = py::none(), py::arg("overwrite") = false,
-     "Write the granules of src that differ from base (every granule "
-     "without a base) to a hipstore delta file");
+     py::arg("base_map") = py::none(), py::arg("map_out") = py::none(),
+     "Write the granules of src that differ from base, or from the state "
+     "recorded in the fingerprint map base_map (every granule without "
+     "either), to a hipstore delta file; map_out also writes the "
+     "fingerprint map of src");
 
   m.def("bdev_import_delta", [](BdevPtr dst, const std::string& path,
                                 bool dry_run) {
@@ -566,6 +589,103 @@ PYBIND11_MODULE(_hipstore, m) {
     if (status != kIoOk) throw_delta("delta_file_info", status, error);
     return delta_info_to_dict(info);
   }, py::arg("path"), "Header fields of a delta file, after its structural checks");
+
+  m.def("fingerprint_bytes", [](py::bytes data, uint32_t granule) {
+    const std::string raw = data;
+    if (granule == 0 || granule % 16 != 0 || raw.size() % granule != 0) {
+      throw std::invalid_argument(
+          "fingerprint_bytes: granule must be a non-zero multiple of 16 that "
+          "divides the data length");
+    }
+    const uint64_t n = raw.size() / granule;
+    std::string out(n * kFingerprintBytes, '\0');
+    {
+      py::gil_scoped_release release;
+      fingerprint_granules(raw.data(), n, granule,
+                           reinterpret_cast<uint8_t*>(&out[0]));
+    }
+    return py::bytes(out);
+  }, py::arg("data"), py::arg("granule"),
+     "Granule fingerprints (16 bytes each) of a bytes object, on the host");
+
+  m.def("bdev_fingerprint", [](BdevPtr bdev, uint32_t granule, uint64_t offset,
+                               uint64_t length, uint64_t staging_bytes,
+                               bool keep) {
+    if (length == 0 && granule != 0 && offset <= bdev->size_bytes()) {
+      length = (bdev->size_bytes() - offset) / granule * granule;
+    }
+    std::string out;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_fingerprint_sync(
+          bdev.get(), offset, length, granule, staging_bytes,
+          [&out, keep](const uint8_t* fps, uint64_t, uint64_t count) {
+            if (keep) {
+              out.append(reinterpret_cast<const char*>(fps),
+                         count * kFingerprintBytes);
+            }
+            return 0;
+          });
+    }
+    if (status != kIoOk) {
+      throw std::runtime_error("bdev_fingerprint failed: status " +
+                               std::to_string(status));
+    }
+    return py::bytes(out);
+  }, py::arg("bdev"), py::arg("granule"), py::arg("offset") = 0,
+     py::arg("length") = 0, py::arg("staging_bytes") = 0,
+     py::arg("keep") = true,
+     "Granule fingerprints (16 bytes each) of a bdev range (on-GPU for HBM "
+     "bdevs). length=0: to the end of the device in whole granules. "
+     "keep=False discards them and returns b'' (tools/fingerprint_bench.py: "
+     "the pass without the host copy)");
+
+  m.def("bdev_fingerprint_file", [](BdevPtr bdev, const std::string& path,
+                                    std::optional<uint32_t> granule,
+                                    bool overwrite) {
+    FingerprintMapInfo info;
+    std::string error;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_fingerprint_file(bdev.get(), path, granule.value_or(0),
+                                     overwrite, &info, &error);
+    }
+    if (status != kIoOk) throw_delta("bdev_fingerprint_file", status, error);
+    return map_info_to_dict(info);
+  }, py::arg("bdev"), py::arg("path"), py::arg("granule") = py::none(),
+     py::arg("overwrite") = false,
+     "Write the fingerprint map of a whole bdev to a file");
+
+  m.def("fingerprint_map_info", [](const std::string& path) {
+    FingerprintMapInfo info;
+    std::string error;
+    const int status = fingerprint_map_info(path, &info, &error);
+    if (status != kIoOk) throw_delta("fingerprint_map_info", status, error);
+    return map_info_to_dict(info);
+  }, py::arg("path"),
+     "Header fields of a fingerprint map, after every check of the file");
+
+  m.def("bdev_verify_fingerprints", [](BdevPtr bdev, const std::string& path,
+                                       uint32_t max_report) {
+    FingerprintVerify r;
+    std::string error;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_verify_fingerprints(bdev.get(), path, max_report, &r,
+                                        &error);
+    }
+    if (status != kIoOk) throw_delta("bdev_verify_fingerprints", status, error);
+    py::dict d;
+    d["granule"] = r.granule;
+    d["granules"] = r.granules;
+    d["mismatched"] = r.mismatched;
+    d["first_mismatches"] = r.first_mismatches;
+    return d;
+  }, py::arg("bdev"), py::arg("path"), py::arg("max_report") = 16,
+     "Recompute a bdev's fingerprints over a map's range and compare");
 
   m.def("replica_scrub", [](BdevPtr bdev, bool repair, uint32_t granule,
                             uint32_t max_report) {

@@ -9,7 +9,10 @@ extended with proxied volume operations).
   oimctl ... unmap --controller gpu-0 vol1
   oimctl ... check --controller gpu-0 vol1
   oimctl ... checkpoint --controller gpu-0 vol1 /backup/vol1.d1 --base vol1-snap
+  oimctl ... checkpoint --controller gpu-0 vol1 /backup/vol1.d2 \
+      --base-map /backup/vol1.map --map-out /backup/vol1.map --overwrite
   oimctl ... restore --controller gpu-0 vol1 /backup/vol1.full
+  oimctl ... verify --controller gpu-0 vol1 /backup/vol1.map
 """
 
 import argparse
@@ -46,6 +49,7 @@ def main(argv=None) -> int:
         ("checkpoint", "write a malloc bdev (or its difference from "
          "--base) to a delta file"),
         ("restore", "apply a delta file to an unmapped malloc bdev"),
+        ("verify", "check a malloc bdev against a fingerprint map"),
         ("list", "list malloc bdevs"),
         ("stats", "per-bdev I/O counters"),
     ):
@@ -67,9 +71,17 @@ def main(argv=None) -> int:
         if name in ("checkpoint", "restore"):
             cmd.add_argument("path", help="delta file on the controller's "
                              "host")
+        if name == "verify":
+            cmd.add_argument("path", help="fingerprint map on the "
+                             "controller's host")
         if name == "checkpoint":
             cmd.add_argument("--base", default="",
                              help="earlier clone: save only what differs")
+            cmd.add_argument("--base-map", default="",
+                             help="fingerprint map of an earlier checkpoint: "
+                             "save only what differs, no clone needed")
+            cmd.add_argument("--map-out", default="",
+                             help="also write the volume's fingerprint map")
             cmd.add_argument("--overwrite", action="store_true")
         if name == "restore":
             cmd.add_argument("--dry-run", action="store_true",
@@ -154,7 +166,8 @@ def main(argv=None) -> int:
                 reply = controller.CheckpointMallocBDev(
                     spec.CheckpointMallocBDevRequest(
                         bdev_name=args.volume, base_name=args.base,
-                        path=args.path, overwrite=args.overwrite),
+                        path=args.path, overwrite=args.overwrite,
+                        base_map=args.base_map, map_out=args.map_out),
                     metadata=metadata, timeout=600)
                 print(f"checkpointed {args.volume} -> {args.path}: "
                       f"{reply.saved} of {reply.granules} granules, "
@@ -168,6 +181,14 @@ def main(argv=None) -> int:
                 verb = "verified" if args.dry_run else "restored"
                 print(f"{verb} {args.volume} <- {args.path}: "
                       f"{reply.applied} of {reply.granules} granules")
+            elif args.command == "verify":
+                reply = controller.VerifyMallocBDev(
+                    spec.VerifyMallocBDevRequest(bdev_name=args.volume,
+                                                 path=args.path),
+                    metadata=metadata, timeout=600)
+                print(f"verified {args.volume} against {args.path}: "
+                      f"{reply.mismatched} of {reply.granules} granules "
+                      "differ")
             elif args.command == "resize":
                 new_size = parse_size(args.size)
                 controller.ResizeMallocBDev(

@@ -398,11 +398,15 @@ class Controller(spec.ControllerServicer):
 
     def CheckpointMallocBDev(self, request, context):
         """oim-amd extension (docs/spec.md): write a volume, or its
-        difference from an earlier clone, to a delta file."""
+        difference from an earlier clone or fingerprint map, to a delta
+        file."""
         name, base, path = request.bdev_name, request.base_name, request.path
         if not name or not path:
             context.abort(grpc.StatusCode.INVALID_ARGUMENT,
                           "bdev_name and path are required")
+        if base and request.base_map:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          "base_name and base_map exclude each other")
         with self._volume_mutex.locked(name):
             with self._client() as client:
                 self._require_bdev(client, name, context)
@@ -411,7 +415,9 @@ class Controller(spec.ControllerServicer):
                 try:
                     result = hipstore.bdev_export_delta(
                         client, name, path, base=base or None,
-                        overwrite=request.overwrite)
+                        overwrite=request.overwrite,
+                        base_map=request.base_map or None,
+                        map_out=request.map_out or None)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.CheckpointMallocBDevReply(
@@ -435,6 +441,24 @@ class Controller(spec.ControllerServicer):
                     self._abort_delta(context, err)
         return spec.RestoreMallocBDevReply(granules=result["granules"],
                                            applied=result["applied"])
+
+    def VerifyMallocBDev(self, request, context):
+        """oim-amd extension (docs/spec.md): check a volume against a
+        fingerprint map."""
+        name, path = request.bdev_name, request.path
+        if not name or not path:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          "bdev_name and path are required")
+        with self._volume_mutex.locked(name):
+            with self._client() as client:
+                self._require_bdev(client, name, context)
+                try:
+                    result = hipstore.bdev_verify_fingerprints(
+                        client, name, path, max_report=0)
+                except hipstore.RpcError as err:
+                    self._abort_delta(context, err)
+        return spec.VerifyMallocBDevReply(granules=result["granules"],
+                                          mismatched=result["mismatched"])
 
     def ListMallocBDevs(self, request, context):
         """oim-amd extension (docs/spec.md): enumerate malloc bdevs."""

@@ -275,15 +275,25 @@ def bdev_replica_scrub(client: Client, name: str, repair: bool = False,
 def bdev_export_delta(client: Client, name: str, path: str,
                       base: Optional[str] = None,
                       granule: Optional[int] = None,
-                      overwrite: bool = False) -> Dict:
+                      overwrite: bool = False,
+                      base_map: Optional[str] = None,
+                      map_out: Optional[str] = None) -> Dict:
     """Checkpoint a volume to a delta file: every granule, or with
-    `base` (an earlier clone) only the granules that differ from it.
+    `base` (an earlier clone) or `base_map` (the fingerprint map written
+    with an earlier checkpoint; no clone needed) only the granules that
+    differ from that state. `map_out` also writes the volume's
+    fingerprint map, the base_map of the next checkpoint.
 
-    Returns {granule, granules, saved, file_bytes, full}. granule
-    defaults to the block size."""
+    Returns {granule, granules, saved, file_bytes, full} and, with
+    map_out, map_bytes. granule defaults to the block size, with
+    base_map to the map's."""
     params: Dict = {"name": name, "path": path}
     if base is not None:
         params["base"] = base
+    if base_map is not None:
+        params["base_map"] = base_map
+    if map_out is not None:
+        params["map_out"] = map_out
     if granule is not None:
         params["granule"] = granule
     if overwrite:
@@ -301,6 +311,35 @@ def bdev_import_delta(client: Client, name: str, path: str,
     if dry_run:
         params["dry_run"] = True
     return client.invoke("bdev_import_delta", params)
+
+
+def bdev_fingerprint(client: Client, name: str, path: str,
+                     granule: Optional[int] = None,
+                     overwrite: bool = False) -> Dict:
+    """Write the fingerprint map of a volume (16 bytes per granule) to a
+    file; HBM volumes are hashed on the GPU.
+
+    Returns {granule, granules, map_bytes}. granule defaults to the
+    block size."""
+    params: Dict = {"name": name, "path": path}
+    if granule is not None:
+        params["granule"] = granule
+    if overwrite:
+        params["overwrite"] = True
+    return client.invoke("bdev_fingerprint", params)
+
+
+def bdev_verify_fingerprints(client: Client, name: str, path: str,
+                             max_report: Optional[int] = None) -> Dict:
+    """Recompute a volume's fingerprints over a map's range and compare
+    (verify a restore, scrub for silent corruption). Read-only; on a
+    claimed volume the answer is advisory.
+
+    Returns {granule, granules, mismatched, first_mismatches}."""
+    params: Dict = {"name": name, "path": path}
+    if max_report is not None:
+        params["max_report"] = max_report
+    return client.invoke("bdev_verify_fingerprints", params)
 
 
 def resize_malloc_bdev(client: Client, name: str, size: int) -> int:

@@ -73,7 +73,8 @@ MESSAGES = [
     Message("ResizeMallocBDevReply", []),
     Message("CheckpointMallocBDevRequest",
             [Field("bdev_name", 1, "string"), Field("base_name", 2, "string"),
-             Field("path", 3, "string"), Field("overwrite", 4, "bool")]),
+             Field("path", 3, "string"), Field("overwrite", 4, "bool"),
+             Field("base_map", 5, "string"), Field("map_out", 6, "string")]),
     Message("CheckpointMallocBDevReply",
             [Field("granules", 1, "int64"), Field("saved", 2, "int64"),
              Field("file_bytes", 3, "int64")]),
@@ -82,6 +83,10 @@ MESSAGES = [
              Field("dry_run", 3, "bool")]),
     Message("RestoreMallocBDevReply",
             [Field("granules", 1, "int64"), Field("applied", 2, "int64")]),
+    Message("VerifyMallocBDevRequest",
+            [Field("bdev_name", 1, "string"), Field("path", 2, "string")]),
+    Message("VerifyMallocBDevReply",
+            [Field("granules", 1, "int64"), Field("mismatched", 2, "int64")]),
     Message("ListMallocBDevsRequest", [Field("prefix", 1, "string")]),
     Message("BDevInfo",
             [Field("name", 1, "string"), Field("size", 2, "int64"),
@@ -120,6 +125,7 @@ SERVICES = [
             ("ResizeMallocBDev", "ResizeMallocBDevRequest", "ResizeMallocBDevReply"),
             ("CheckpointMallocBDev", "CheckpointMallocBDevRequest", "CheckpointMallocBDevReply"),
             ("RestoreMallocBDev", "RestoreMallocBDevRequest", "RestoreMallocBDevReply"),
+            ("VerifyMallocBDev", "VerifyMallocBDevRequest", "VerifyMallocBDevReply"),
             ("ListMallocBDevs", "ListMallocBDevsRequest", "ListMallocBDevsReply"),
             ("GetIOStats", "GetIOStatsRequest", "GetIOStatsReply"),
         ],
@@ -155,6 +161,8 @@ CheckpointMallocBDevRequest = _classes["CheckpointMallocBDevRequest"]
 CheckpointMallocBDevReply = _classes["CheckpointMallocBDevReply"]
 RestoreMallocBDevRequest = _classes["RestoreMallocBDevRequest"]
 RestoreMallocBDevReply = _classes["RestoreMallocBDevReply"]
+VerifyMallocBDevRequest = _classes["VerifyMallocBDevRequest"]
+VerifyMallocBDevReply = _classes["VerifyMallocBDevReply"]
 ListMallocBDevsRequest = _classes["ListMallocBDevsRequest"]
 BDevInfo = _classes["BDevInfo"]
 ListMallocBDevsReply = _classes["ListMallocBDevsReply"]

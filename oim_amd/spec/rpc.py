@@ -54,6 +54,8 @@ class ControllerStub:
             "CheckpointMallocBDev", pb.CheckpointMallocBDevReply)
         self.RestoreMallocBDev = method(
             "RestoreMallocBDev", pb.RestoreMallocBDevReply)
+        self.VerifyMallocBDev = method(
+            "VerifyMallocBDev", pb.VerifyMallocBDevReply)
         self.ListMallocBDevs = method("ListMallocBDevs", pb.ListMallocBDevsReply)
         self.GetIOStats = method("GetIOStats", pb.GetIOStatsReply)
 
@@ -95,6 +97,9 @@ class ControllerServicer:
     def RestoreMallocBDev(self, request, context):
         context.abort(grpc.StatusCode.UNIMPLEMENTED, "RestoreMallocBDev not implemented")
 
+    def VerifyMallocBDev(self, request, context):
+        context.abort(grpc.StatusCode.UNIMPLEMENTED, "VerifyMallocBDev not implemented")
+
     def ListMallocBDevs(self, request, context):
         context.abort(grpc.StatusCode.UNIMPLEMENTED, "ListMallocBDevs not implemented")
 
@@ -134,6 +139,8 @@ def add_controller_to_server(servicer: ControllerServicer, server: grpc.Server) 
             servicer.CheckpointMallocBDev, pb.CheckpointMallocBDevRequest),
         "RestoreMallocBDev": _unary(
             servicer.RestoreMallocBDev, pb.RestoreMallocBDevRequest),
+        "VerifyMallocBDev": _unary(
+            servicer.VerifyMallocBDev, pb.VerifyMallocBDevRequest),
         "ListMallocBDevs": _unary(servicer.ListMallocBDevs, pb.ListMallocBDevsRequest),
         "GetIOStats": _unary(servicer.GetIOStats, pb.GetIOStatsRequest),
     }
