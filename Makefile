@@ -23,7 +23,7 @@ HIP_HDRS := $(HDRS) native/src/gpu_internal.h
 CORE_OBJS := $(B)/json.o $(B)/bdev.o $(B)/crc32c.o $(B)/rpc_server.o \
              $(B)/methods.o $(B)/nbd.o $(B)/ublk.o $(B)/composite.o $(B)/vhost.o $(B)/vhost_master.o \
              $(B)/nvmf_common.o $(B)/nvmf_target.o $(B)/nvmf_initiator.o \
-             $(B)/rados_client.o $(B)/rados_cluster.o $(B)/delta.o \
+             $(B)/rados_client.o $(B)/rados_cluster.o $(B)/checked_file.o $(B)/delta.o \
              $(B)/fingerprint.o $(B)/gpu.o $(B)/bulk_ops.o
 
 .PHONY: all clean

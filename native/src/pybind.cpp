@@ -190,8 +190,18 @@ py::dict map_info_to_dict(const FingerprintMapInfo& info) {
   return d;
 }
 
-[[noreturn]] void throw_delta(const char* what, int status,
-                              const std::string& error) {
+// Runs a call of the delta layer (delta.h), which takes the error string
+// and returns a status, with the GIL released; kIoInvalid becomes
+// ValueError, any other failure RuntimeError.
+template <typename Call>
+void delta_call(const char* what, Call call) {
+  std::string error;
+  int status;
+  {
+    py::gil_scoped_release release;
+    status = call(&error);
+  }
+  if (status == kIoOk) return;
   const std::string text = std::string(what) + ": " + error + " (status " +
                            std::to_string(status) + ")";
   if (status == kIoInvalid) throw std::invalid_argument(text);
@@ -547,15 +557,11 @@ PYBIND11_MODULE(_hipstore, m) {
     DeltaMaps maps;
     maps.base_map = base_map.value_or("");
     maps.map_out = map_out.value_or("");
-    std::string error;
-    int status;
-    {
-      py::gil_scoped_release release;
-      status = bdev_export_delta(src.get(), base ? base->get() : nullptr,
-                                 path, granule.value_or(0), overwrite, &maps,
-                                 &info, &error);
-    }
-    if (status != kIoOk) throw_delta("bdev_export_delta", status, error);
+    delta_call("bdev_export_delta", [&](std::string* error) {
+      return bdev_export_delta(src.get(), base ? base->get() : nullptr, path,
+                               granule.value_or(0), overwrite, &maps, &info,
+                               error);
+    });
     py::dict d = delta_info_to_dict(info);
     if (!maps.map_out.empty()) d["map_bytes"] = maps.map_bytes;
     return d;
@@ -570,13 +576,9 @@ PYBIND11_MODULE(_hipstore, m) {
   m.def("bdev_import_delta", [](BdevPtr dst, const std::string& path,
                                 bool dry_run) {
     DeltaInfo info;
-    std::string error;
-    int status;
-    {
-      py::gil_scoped_release release;
-      status = bdev_import_delta(dst.get(), path, dry_run, &info, &error);
-    }
-    if (status != kIoOk) throw_delta("bdev_import_delta", status, error);
+    delta_call("bdev_import_delta", [&](std::string* error) {
+      return bdev_import_delta(dst.get(), path, dry_run, &info, error);
+    });
     return delta_info_to_dict(info);
   }, py::arg("dst"), py::arg("path"), py::arg("dry_run") = false,
      "Apply a hipstore delta file to dst; dry_run checks everything and "
@@ -584,9 +586,9 @@ PYBIND11_MODULE(_hipstore, m) {
 
   m.def("delta_file_info", [](const std::string& path) {
     DeltaInfo info;
-    std::string error;
-    const int status = delta_file_info(path, &info, &error);
-    if (status != kIoOk) throw_delta("delta_file_info", status, error);
+    delta_call("delta_file_info", [&](std::string* error) {
+      return delta_file_info(path, &info, error);
+    });
     return delta_info_to_dict(info);
   }, py::arg("path"), "Header fields of a delta file, after its structural checks");
 
@@ -645,14 +647,10 @@ PYBIND11_MODULE(_hipstore, m) {
                                     std::optional<uint32_t> granule,
                                     bool overwrite) {
     FingerprintMapInfo info;
-    std::string error;
-    int status;
-    {
-      py::gil_scoped_release release;
-      status = bdev_fingerprint_file(bdev.get(), path, granule.value_or(0),
-                                     overwrite, &info, &error);
-    }
-    if (status != kIoOk) throw_delta("bdev_fingerprint_file", status, error);
+    delta_call("bdev_fingerprint_file", [&](std::string* error) {
+      return bdev_fingerprint_file(bdev.get(), path, granule.value_or(0),
+                                   overwrite, &info, error);
+    });
     return map_info_to_dict(info);
   }, py::arg("bdev"), py::arg("path"), py::arg("granule") = py::none(),
      py::arg("overwrite") = false,
@@ -660,9 +658,9 @@ PYBIND11_MODULE(_hipstore, m) {
 
   m.def("fingerprint_map_info", [](const std::string& path) {
     FingerprintMapInfo info;
-    std::string error;
-    const int status = fingerprint_map_info(path, &info, &error);
-    if (status != kIoOk) throw_delta("fingerprint_map_info", status, error);
+    delta_call("fingerprint_map_info", [&](std::string* error) {
+      return fingerprint_map_info(path, &info, error);
+    });
     return map_info_to_dict(info);
   }, py::arg("path"),
      "Header fields of a fingerprint map, after every check of the file");
@@ -670,14 +668,9 @@ PYBIND11_MODULE(_hipstore, m) {
   m.def("bdev_verify_fingerprints", [](BdevPtr bdev, const std::string& path,
                                        uint32_t max_report) {
     FingerprintVerify r;
-    std::string error;
-    int status;
-    {
-      py::gil_scoped_release release;
-      status = bdev_verify_fingerprints(bdev.get(), path, max_report, &r,
-                                        &error);
-    }
-    if (status != kIoOk) throw_delta("bdev_verify_fingerprints", status, error);
+    delta_call("bdev_verify_fingerprints", [&](std::string* error) {
+      return bdev_verify_fingerprints(bdev.get(), path, max_report, &r, error);
+    });
     py::dict d;
     d["granule"] = r.granule;
     d["granules"] = r.granules;

@@ -446,6 +446,58 @@ class TestChain:
         assert sorted(os.listdir(tmp_path)) == ["m"]
 
 
+class TestPublishAndCleanup:
+    """What is left behind when a file cannot take its final name."""
+
+    def test_delta_path_is_a_directory(self, volume, tmp_path):
+        os.mkdir(tmp_path / "dir")
+        with pytest.raises(RuntimeError):
+            hs.bdev_export_delta(volume["bdev"], str(tmp_path / "dir"),
+                                 overwrite=True, map_out=str(tmp_path / "m"))
+        assert os.listdir(tmp_path) == ["dir"]
+        assert os.listdir(tmp_path / "dir") == []
+
+    def test_map_path_is_a_directory(self, volume, tmp_path):
+        os.mkdir(tmp_path / "mapdir")
+        with pytest.raises(RuntimeError, match="was written"):
+            hs.bdev_export_delta(volume["bdev"], str(tmp_path / "d"),
+                                 overwrite=True,
+                                 map_out=str(tmp_path / "mapdir"))
+        assert open(tmp_path / "d", "rb").read() == \
+            build_delta_file(volume["data"], BLOCK)
+        assert sorted(os.listdir(tmp_path)) == ["d", "mapdir"]
+        assert os.listdir(tmp_path / "mapdir") == []
+
+    def test_fingerprint_file_to_a_directory(self, volume, tmp_path):
+        os.mkdir(tmp_path / "mapdir")
+        with pytest.raises(RuntimeError):
+            hs.bdev_fingerprint_file(volume["bdev"], str(tmp_path / "mapdir"),
+                                     overwrite=True)
+        assert os.listdir(tmp_path) == ["mapdir"]
+        assert os.listdir(tmp_path / "mapdir") == []
+
+    def test_info_calls_on_a_directory(self, tmp_path):
+        with pytest.raises(ValueError):
+            hs.delta_file_info(str(tmp_path))
+        with pytest.raises(ValueError):
+            hs.fingerprint_map_info(str(tmp_path))
+
+    def test_same_path_for_base_map_and_map_out(self, tmp_path):
+        data = bytearray(random_bytes(N * BLOCK, 12))
+        bdev = hs.create_malloc_bdev("fp-same", BLOCK, N)
+        bdev.write(0, bytes(data))
+        m = str(tmp_path / "m")
+        hs.bdev_fingerprint_file(bdev, m)
+        data[70 * BLOCK:71 * BLOCK] = b"\x3C" * BLOCK
+        bdev.write(70 * BLOCK, b"\x3C" * BLOCK)
+        r = hs.bdev_export_delta(bdev, str(tmp_path / "d"), base_map=m,
+                                 map_out=m, overwrite=True)
+        assert r["marked"] == 1
+        assert open(m, "rb").read() == build_map_file(bytes(data), BLOCK)
+        assert hs.bdev_verify_fingerprints(bdev, m)["mismatched"] == 0
+        assert sorted(os.listdir(tmp_path)) == ["d", "m"]
+
+
 # --- the daemon, oim.v0 and oimctl ---------------------------------------------
 
 class TestDaemon:
