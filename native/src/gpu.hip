@@ -100,8 +100,9 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_copy_blocks(
 // MI355X-native equivalent puts the poller ON the GPU: one persistent
 // launch per queue whose waves claim submission-ring descriptors with a
 // device-scope atomic (dequeue ~0.25-1.1 us, MI355X_MICROARCH price
-// list), copy the 4 KiB tile through LDS, and publish a completion word
-// to pinned host memory with a system-scope release. Submission latency
+// list), move the 4 KiB tiles through registers with write-through
+// stores, and publish completion words to pinned host memory once the
+// wave's stores have drained (serve_run). Submission latency
 // becomes host-store -> PCIe poll -> copy (~5-10 us) instead of a
 // kernel launch per batch.
 //
@@ -112,35 +113,182 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_copy_blocks(
 // idempotent (same copy, same completion value), so the handoff is
 // race-free without any further coordination.
 
-__device__ __forceinline__ unsigned long long wave_bcast_u64(
-    unsigned long long v) {
-  int lo = __shfl(static_cast<int>(v & 0xFFFFFFFFu), 0);
-  int hi = __shfl(static_cast<int>(v >> 32), 0);
+__device__ __forceinline__ unsigned long long wave_shfl_u64(
+    unsigned long long v, uint32_t src_lane) {
+  const int from = static_cast<int>(src_lane);
+  int lo = __shfl(static_cast<int>(v & 0xFFFFFFFFu), from);
+  int hi = __shfl(static_cast<int>(v >> 32), from);
   return (static_cast<unsigned long long>(static_cast<uint32_t>(hi)) << 32) |
          static_cast<uint32_t>(lo);
 }
 
-// Bounded CAS claim, shared by both resident kernels: take index `c`
-// of a ring only while the leader has published work past it
-// (`c < kt`, claim-only-when-available). The original blind
-// fetch_add-then-wait form wedged the serving wave on current pool
-// firmware (round-2 diagnosis, tools/engine_diag*.sh), and in the
-// shared service it would park a worker on one ring while others have
-// work. Lane 0 does the CAS, the wave follows its result. Returns the
-// claimed index, or ~0 when the ring has nothing left.
-__device__ __forceinline__ unsigned long long claim_bounded(
+// Everything a resident kernel moves is global memory (HBM or pinned
+// host): global_ instructions, never flat_.
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+typedef const __attribute__((address_space(1))) unsigned long long cgu64;
+
+__device__ __forceinline__ gu64* as_global(const volatile void* p) {
+  return reinterpret_cast<gu64*>(reinterpret_cast<uintptr_t>(p));
+}
+
+// Upper bound of HIPSTORE_BATCH_TILES: the 3 x 8 descriptor words of a
+// run are fetched by one wave-wide load, its 8 completion words by one
+// wave-wide store.
+constexpr uint32_t kMaxRunTiles = 8;
+
+// Bounded CAS claim of a RUN of consecutive ring indices, shared by
+// both resident kernels: take [c, c + n) only while the leader has
+// published work past it (`c < kt`, claim-only-when-available, never
+// past `kt`). The original blind fetch_add-then-wait form wedged the
+// serving wave on current pool firmware (round-2 diagnosis,
+// tools/engine_diag*.sh), and in the shared service it would park a
+// worker on one ring while others have work. Lane 0 does the CAS, the
+// wave follows its result.
+//
+// n = min(batch, ceil(backlog / workers)): a backlog no larger than
+// the worker count is still spread one tile per wave (QD=1 latency and
+// shallow queues see the unbatched engine), runs form only when the
+// ring is deeper than the waves serving it. batch == 1 is the
+// unbatched form of the same code. Returns the first claimed index and
+// sets *n_out, or returns ~0 when the ring has nothing left.
+__device__ __forceinline__ unsigned long long claim_run(
     unsigned long long* counter, unsigned long long c,
-    unsigned long long kt, uint32_t lane) {
+    unsigned long long kt, uint32_t workers, uint32_t batch, uint32_t lane,
+    uint32_t* n_out) {
   while (c < kt) {
+    const unsigned long long cap =
+        static_cast<unsigned long long>(batch) * workers;
+    const uint32_t backlog =
+        static_cast<uint32_t>(kt - c < cap ? kt - c : cap);
+    const uint32_t n = (backlog + workers - 1) / workers;  // 1..batch
     unsigned long long witnessed = 0;
     if (lane == 0) {
-      witnessed = atomicCAS(counter, c, c + 1);
+      witnessed = atomicCAS(counter, c, c + n);
     }
-    witnessed = wave_bcast_u64(witnessed);
-    if (witnessed == c) return c;
+    witnessed = wave_shfl_u64(witnessed, 0);
+    if (witnessed == c) {
+      *n_out = n;
+      return c;
+    }
     c = witnessed;
   }
   return ~0ull;
+}
+
+// One tile through registers, lane l moving the 8-byte words l, l + 64,
+// ... of it: all loads issued before the first store, every store a
+// system-scope atomic store (write-through; serve_run's completion
+// depends on that). A null `src_word` is a fill. One code path under a
+// per-lane bound `i < n8`; kFull instantiates it for whole tiles with
+// the bound folded away, because the compiler branches around each
+// bounded store and then drains vmcnt before the next one, which would
+// chain the eight stores of the common 4 KiB tile.
+template <bool kFull>
+__device__ __forceinline__ void move_tile(
+    unsigned long long src_word, unsigned long long dst_word, uint32_t n8,
+    unsigned long long fill64, uint32_t lane) {
+  unsigned long long v[8];
+#pragma unroll
+  for (uint32_t k = 0; k < 8; ++k) v[k] = fill64;
+  if (src_word != 0) {
+    cgu64* src = reinterpret_cast<cgu64*>(src_word);
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+      const uint32_t i = lane + 64 * k;
+      if (kFull || i < n8) {
+        v[k] = __hip_atomic_load(src + i, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  gu64* dst = reinterpret_cast<gu64*>(dst_word);
+  // The bounded form stores from the last word down: with the same
+  // order in both forms the compiler merges their final stores into one
+  // block and puts the bounded form's vmcnt drain in front of it, for
+  // whole tiles too.
+#pragma unroll
+  for (uint32_t j = 0; j < 8; ++j) {
+    const uint32_t k = kFull ? j : 7 - j;
+    const uint32_t i = lane + 64 * k;
+    if (kFull || i < n8) {
+      __hip_atomic_store(dst + i, v[k], __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// Serves the run [claim, claim + n) of one ring, 1 <= n <= kMaxRunTiles,
+// on one wave: descriptors, payload, completions.
+//
+// Descriptors: ONE wave-wide load fetches all 3n words (lane l reads
+// word l % 3 of ring slot (claim + l / 3) & ring_mask, so a run that
+// straddles the ring end is no special case) — one PCIe round trip per
+// run. The load is a relaxed system-scope atomic: host memory is
+// uncached on the GPU side, so the value is current, and its address
+// depends on the CAS result, so the compiler cannot hoist it above the
+// claim and read a slot before the host wrote it (seen as null-dst
+// faults / phantom zero-byte completions when these were plain loads).
+// The words reach the other lanes with __shfl.
+//
+// Payload: through registers, 8 bytes per lane, all eight loads of a
+// tile issued before the first store. Loads are agent-scope (sc1,
+// L1-bypassing): a RESIDENT kernel has no dispatch boundaries, so a
+// plain load can hit a stale line written around by another CU's wave
+// (caught as a read-after-write corruption by TestVhostHbm). Batched
+// kernels don't need this — each dispatch's implicit acquire
+// invalidates the caches. Fills and partial tiles (`bytes` a multiple
+// of 16, down to 16) take the same path under the per-lane bound.
+//
+// Completion, once per run: EVERY payload store above is a
+// system-scope atomic store (sc0 sc1, write-through), for HBM
+// destinations as much as for host ones, so after the wave has drained
+// its own stores (s_waitcnt vmcnt(0)) the bytes are in memory and the
+// CQ words may follow as relaxed stores: lanes 0..n-1 write the run's
+// n adjacent words with one instruction. There is no release fence and
+// no L2 writeback, and that is only sound while no payload store is a
+// plain one: a line left dirty in this XCD's L2 would be read stale
+// from HBM by a worker on another XCD after the host saw the
+// completion. The hand-off also relies on one-wave workgroups (the
+// wave that stored is the wave that drains and signals). Do not put a
+// __threadfence_system() here: it is not needed, and on the current
+// pool firmware it HANGS the wave — round-2 diagnosis
+// (tools/engine_diag3.sh) showed the serving wave copying the data
+// correctly, then never publishing the CQ nor claiming again, with the
+// fence the only instruction between those two points.
+__device__ __forceinline__ void serve_run(
+    const BlockDesc* sq, volatile unsigned long long* cq, uint32_t ring_mask,
+    unsigned long long claim, uint32_t n, uint32_t lane) {
+  static_assert(3 * kMaxRunTiles <= 64, "descriptor words of a run: one load");
+  static_assert(kTileBytes == 8 * 64 * 8, "8 x u64 per lane per tile");
+  const uint32_t my_tile = lane / 3;
+  const uint32_t my_word = lane - 3 * my_tile;
+  unsigned long long word = 0;
+  if (lane < 3 * n) {
+    cgu64* slot =
+        as_global(sq) + 3ull * ((claim + my_tile) & ring_mask) + my_word;
+    word = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  for (uint32_t t = 0; t < n; ++t) {
+    const unsigned long long w0 = wave_shfl_u64(word, 3 * t);      // src
+    const unsigned long long w1 = wave_shfl_u64(word, 3 * t + 1);  // dst
+    const unsigned long long w2 = wave_shfl_u64(word, 3 * t + 2);  // bytes|fill
+    const uint32_t n8 = static_cast<uint32_t>(w2 & 0xFFFFFFFFu) >> 3;
+    const uint32_t b = static_cast<uint32_t>(w2 >> 32) & 0xFF;
+    const uint32_t fill32 = b | (b << 8) | (b << 16) | (b << 24);
+    const unsigned long long fill64 =
+        fill32 | (static_cast<unsigned long long>(fill32) << 32);
+    if (n8 == kTileBytes / 8) {
+      move_tile<true>(w0, w1, n8, fill64, lane);
+    } else {
+      move_tile<false>(w0, w1, n8, fill64, lane);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane < n) {
+    const unsigned long long index = claim + lane;
+    __hip_atomic_store(as_global(&cq[index & ring_mask]), index + 1,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
 }
 
 struct PersistentCtl {
@@ -160,12 +308,14 @@ struct PersistentCtl {
   uint32_t* exit_flag;                // leader-published stop/idle exit
   uint32_t ring_mask;
   uint32_t idle_spins;         // leader spins before self-exit
+  uint32_t batch_tiles;        // longest run one wave claims, 1..kMaxRunTiles
 };
 
+// One-wave workgroups: serve_run()'s completion hand-off (the wave's own
+// vmcnt drain, then its CQ stores) covers exactly the stores of the
+// signalling wave. More waves per workgroup would need a barrier there.
 __global__ __launch_bounds__(64) void k_persistent_copy(PersistentCtl ctl) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[kTileBytes];
   const uint32_t lane = threadIdx.x & 63;
-  float4* lds = reinterpret_cast<float4*>(lds_raw);
 
   if (blockIdx.x == 0) {
     // Leader wave: the only PCIe poller. Mirrors sq_tail into device
@@ -196,13 +346,15 @@ __global__ __launch_bounds__(64) void k_persistent_copy(PersistentCtl ctl) {
     }
   }
 
+  const uint32_t workers = gridDim.x - 1;
   while (true) {
     const unsigned long long kt = __hip_atomic_load(
         ctl.known_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long c = __hip_atomic_load(
         ctl.claim_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long claim =
-        claim_bounded(ctl.claim_counter, c, kt, lane);
+    uint32_t n = 0;
+    const unsigned long long claim = claim_run(
+        ctl.claim_counter, c, kt, workers, ctl.batch_tiles, lane, &n);
     if (claim == ~0ull) {
       if (__hip_atomic_load(ctl.exit_flag, __ATOMIC_RELAXED,
                             __HIP_MEMORY_SCOPE_AGENT) != 0) {
@@ -211,68 +363,7 @@ __global__ __launch_bounds__(64) void k_persistent_copy(PersistentCtl ctl) {
       __builtin_amdgcn_s_sleep(16);
       continue;
     }
-    // Volatile loads: the descriptor address is computable BEFORE the
-    // wait loop, so a plain load could be hoisted above it by the
-    // compiler and read the slot before the host wrote it (observed as
-    // null-dst faults / phantom zero-byte completions). Volatile pins
-    // the reads after the tail match; host memory is uncached on the
-    // GPU side, so the values are then current by construction. Three
-    // independent u64 loads pipeline over PCIe (vs 4 dependent field
-    // reads at ~1 us each).
-    const volatile unsigned long long* vd =
-        reinterpret_cast<const volatile unsigned long long*>(
-            &ctl.sq[claim & ctl.ring_mask]);
-    const unsigned long long w0 = vd[0];
-    const unsigned long long w1 = vd[1];
-    const unsigned long long w2 = vd[2];
-    BlockDesc d;
-    d.src = reinterpret_cast<const uint8_t*>(w0);
-    d.dst = reinterpret_cast<uint8_t*>(w1);
-    d.bytes = static_cast<uint32_t>(w2 & 0xFFFFFFFFu);
-    d.fill = static_cast<uint32_t>(w2 >> 32);
-    // Uniform u64 tile path, each lane staging and draining ITS OWN
-    // LDS slots (slot i covered by lane i%64 in both loops — no
-    // cross-lane LDS dependency, so wave-internal lgkmcnt ordering is
-    // the only sync needed). Loads are agent-scope (sc1,
-    // L2-bypassing): a RESIDENT kernel has no dispatch boundaries, so
-    // a plain load can hit a stale line in this XCD's L2 written
-    // around by another XCD's wave (caught as a read-after-write
-    // corruption by TestVhostHbm). Batched kernels don't need this —
-    // each dispatch's implicit acquire invalidates the caches.
-    const uint32_t n8 = d.bytes >> 3;
-    unsigned long long* lds64 = reinterpret_cast<unsigned long long*>(lds);
-    if (d.src != nullptr) {
-      const unsigned long long* __restrict__ src =
-          reinterpret_cast<const unsigned long long*>(d.src);
-#pragma unroll 4
-      for (uint32_t i = lane; i < n8; i += 64) {
-        lds64[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-      }
-    } else {
-      const uint32_t b = d.fill & 0xFF;
-      const uint32_t word = b | (b << 8) | (b << 16) | (b << 24);
-      const unsigned long long v =
-          word | (static_cast<unsigned long long>(word) << 32);
-      for (uint32_t i = lane; i < n8; i += 64) lds64[i] = v;
-    }
-    unsigned long long* __restrict__ dst =
-        reinterpret_cast<unsigned long long*>(d.dst);
-#pragma unroll 4
-    for (uint32_t i = lane; i < n8; i += 64) dst[i] = lds64[i];
-    // Publish the completion: data must be host-visible before the CQ
-    // word. The system-scope RELEASE store carries that ordering by
-    // itself (s_waitcnt on the wave's outstanding stores + L2
-    // writeback before the store). An explicit __threadfence_system()
-    // here is redundant — and on the current pool firmware it HANGS
-    // the wave: round-2 diagnosis (tools/engine_diag3.sh) showed the
-    // serving wave copying the data correctly, then never publishing
-    // the CQ nor claiming again, with the fence the only instruction
-    // between those two points. Do not reintroduce it.
-    if (lane == 0) {
-      __hip_atomic_store(&ctl.cq[claim & ctl.ring_mask], claim + 1,
-                         __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    serve_run(ctl.sq, ctl.cq, ctl.ring_mask, claim, n, lane);
   }
 }
 
@@ -329,6 +420,7 @@ struct SharedCtl {
   volatile uint32_t* stop;      // pinned host
   uint32_t* exit_flag;          // device
   uint32_t idle_spins;
+  uint32_t batch_tiles;         // longest run one wave claims, 1..kMaxRunTiles
 };
 
 // Slot fields as 8-byte words for uniform agent-scope access (sc1
@@ -348,10 +440,10 @@ __device__ __forceinline__ void slot_st(SharedSlot* slot, int word,
                      value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// One-wave workgroups, as in k_persistent_copy: serve_run()'s completion
+// hand-off relies on it.
 __global__ __launch_bounds__(64) void k_shared_service(SharedCtl ctl) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[kTileBytes];
   const uint32_t lane = threadIdx.x & 63;
-  float4* lds = reinterpret_cast<float4*>(lds_raw);
 
   if (blockIdx.x == 0) {
     // Leader wave: lane l mirrors slot l's host tail — a full sweep of
@@ -392,11 +484,12 @@ __global__ __launch_bounds__(64) void k_shared_service(SharedCtl ctl) {
     }
   }
 
-  // Worker wave: sweep the slots, claim and serve at most one
-  // descriptor per slot per sweep (fairness across rings). A bounded
+  // Worker wave: sweep the slots, claim and serve at most one run of
+  // descriptors per slot per sweep (fairness across rings). A bounded
   // CAS claims work only when available — a blind fetch_add would park
   // this worker on one ring while others have work.
   const uint32_t start = blockIdx.x;  // stagger sweep origins
+  const uint32_t workers = gridDim.x - 1;
   while (true) {
     bool progress = false;
     for (uint32_t i = 0; i < kSharedSlots; ++i) {
@@ -406,54 +499,14 @@ __global__ __launch_bounds__(64) void k_shared_service(SharedCtl ctl) {
       const uint32_t ring_mask = static_cast<uint32_t>(ma);
       const unsigned long long kt = slot_ld(slot, 4);
       const unsigned long long c = slot_ld(slot, 3);
-      const unsigned long long claim =
-          claim_bounded(&slot->claim, c, kt, lane);
+      uint32_t n = 0;
+      const unsigned long long claim = claim_run(
+          &slot->claim, c, kt, workers, ctl.batch_tiles, lane, &n);
       if (claim == ~0ull) continue;
-      // Serve it (volatile loads: pinned after the claim, never hoisted).
       const BlockDesc* sq = reinterpret_cast<const BlockDesc*>(slot_ld(slot, 0));
-      const volatile unsigned long long* vd =
-          reinterpret_cast<const volatile unsigned long long*>(
-              &sq[claim & ring_mask]);
-      const unsigned long long w0 = vd[0];
-      const unsigned long long w1 = vd[1];
-      const unsigned long long w2 = vd[2];
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(w0);
-      uint8_t* dst = reinterpret_cast<uint8_t*>(w1);
-      const uint32_t bytes = static_cast<uint32_t>(w2 & 0xFFFFFFFFu);
-      // Uniform u64 same-slot tile path with agent-scope loads:
-      // resident-kernel cross-XCD coherence, see the per-queue
-      // kernel's copy loop.
-      const uint32_t n8 = bytes >> 3;
-      unsigned long long* lds64 =
-          reinterpret_cast<unsigned long long*>(lds);
-      if (src != nullptr) {
-        const unsigned long long* __restrict__ s8 =
-            reinterpret_cast<const unsigned long long*>(src);
-#pragma unroll 4
-        for (uint32_t k = lane; k < n8; k += 64) {
-          lds64[k] = __hip_atomic_load(s8 + k, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-        }
-      } else {
-        const uint32_t b = static_cast<uint32_t>(w2 >> 32) & 0xFF;
-        const uint32_t word = b | (b << 8) | (b << 16) | (b << 24);
-        const unsigned long long v =
-            word | (static_cast<unsigned long long>(word) << 32);
-        for (uint32_t k = lane; k < n8; k += 64) lds64[k] = v;
-      }
-      unsigned long long* __restrict__ d8 =
-          reinterpret_cast<unsigned long long*>(dst);
-#pragma unroll 4
-      for (uint32_t k = lane; k < n8; k += 64) d8[k] = lds64[k];
-      // Ordering carried by the system-scope release store; see the
-      // per-queue kernel's publish comment (explicit
-      // __threadfence_system hangs waves on current pool firmware).
-      if (lane == 0) {
-        volatile unsigned long long* cq =
-            reinterpret_cast<volatile unsigned long long*>(slot_ld(slot, 2));
-        __hip_atomic_store(&cq[claim & ring_mask], claim + 1,
-                           __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      volatile unsigned long long* cq =
+          reinterpret_cast<volatile unsigned long long*>(slot_ld(slot, 2));
+      serve_run(sq, cq, ring_mask, claim, n, lane);
       progress = true;
     }
     if (!progress) {
@@ -1114,23 +1167,36 @@ inline bool fallback_is_shared() {
   return shared;
 }
 
+// Longest run of ring indices one worker wave claims at a time
+// (HIPSTORE_BATCH_TILES, 1..kMaxRunTiles; 1 = one tile per claim).
+// Default 2: 4 queues x 64 KiB rise from 37 to 56 GB/s between 1 and 2
+// and by less than run-to-run spread beyond (profiles/README.md,
+// "Descriptor runs on the resident engines").
+inline uint32_t batch_tiles_env() {
+  const char* env = getenv("HIPSTORE_BATCH_TILES");
+  const int v = env ? atoi(env) : 2;
+  return static_cast<uint32_t>(
+      std::min(std::max(v, 1), static_cast<int>(kMaxRunTiles)));
+}
+
 class HbmPersistentChannel : public ServiceRingChannel {
  public:
   static constexpr uint32_t kIdleSpins = 500000;  // ~1 s of s_sleep polling
 
   // Worker waves per queue (1-wave workgroups). 16 default; QD-deep
   // queues benefit from more (HIPSTORE_PERSISTENT_WORKERS overrides).
-  static uint32_t workers() {
-    static uint32_t w = [] {
-      const char* env = getenv("HIPSTORE_PERSISTENT_WORKERS");
-      int v = env ? atoi(env) : 16;
-      return static_cast<uint32_t>(std::min(std::max(v, 1), 64));
-    }();
-    return w;
+  // Read when the channel is created, like HIPSTORE_BATCH_TILES.
+  static uint32_t workers_env() {
+    const char* env = getenv("HIPSTORE_PERSISTENT_WORKERS");
+    int v = env ? atoi(env) : 16;
+    return static_cast<uint32_t>(std::min(std::max(v, 1), 64));
   }
 
   HbmPersistentChannel(int device, uint8_t* base)
-      : ServiceRingChannel(base), device_(device) {
+      : ServiceRingChannel(base),
+        device_(device),
+        workers_(workers_env()),
+        batch_tiles_(batch_tiles_env()) {
     // The creator (HbmBdev::get_channel) claimed the per-device slot
     // with fetch_add BEFORE constructing; release it in the dtor.
     HIP_CHECK(hipSetDevice(device));
@@ -1211,7 +1277,8 @@ class HbmPersistentChannel : public ServiceRingChannel {
     ctl.exit_flag = reinterpret_cast<uint32_t*>(claim_ctr_ + 2);
     ctl.ring_mask = kRing - 1;
     ctl.idle_spins = kIdleSpins;
-    hipLaunchKernelGGL(k_persistent_copy, dim3(workers() + 1), dim3(64), 0,
+    ctl.batch_tiles = batch_tiles_;
+    hipLaunchKernelGGL(k_persistent_copy, dim3(workers_ + 1), dim3(64), 0,
                        stream_, ctl);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
@@ -1253,6 +1320,8 @@ class HbmPersistentChannel : public ServiceRingChannel {
   hipStream_t dbg_stream_ = nullptr;
 
   int device_;
+  const uint32_t workers_;      // worker waves of this channel's kernel
+  const uint32_t batch_tiles_;  // longest run one of them claims
   hipStream_t stream_ = nullptr;
   volatile uint32_t* stop_ = nullptr;
   unsigned long long* claim_ctr_ = nullptr;
@@ -1404,6 +1473,9 @@ class SharedService {
     ctl.stop = device_view(const_cast<uint32_t*>(stop_));
     ctl.exit_flag = exit_flag_dev_;
     ctl.idle_spins = kIdleSpins;
+    // One kernel serves every shared channel of the device, so its run
+    // length is read per launch, like its worker count.
+    ctl.batch_tiles = batch_tiles_env();
     const char* env = getenv("HIPSTORE_SHARED_WORKERS");
     int workers = env ? atoi(env) : 48;
     workers = std::min(std::max(workers, 1), 255);
@@ -2500,6 +2572,7 @@ std::map<std::string, long long> persistent_kernel_probe(int device,
   ctl.exit_flag = reinterpret_cast<uint32_t*>(claim_ctr + 2);
   ctl.ring_mask = kProbeRing - 1;
   ctl.idle_spins = 500000;
+  ctl.batch_tiles = 1;
   hipLaunchKernelGGL(k_persistent_copy, dim3(17), dim3(64), 0, stream, ctl);
   r["launch_err"] = static_cast<long long>(hipGetLastError());
   // One descriptor.
