@@ -235,6 +235,43 @@ def run_checked(q, model, ops):
     return results
 
 
+class RecordingQueue:
+    """An hs.IoQueue that keeps the ops of every run() it passes on, so
+    a test can state conditions on what a scenario actually submitted
+    (which replica its reads were routed to, say)."""
+
+    def __init__(self, queue):
+        self.queue = queue
+        self.runs = []
+
+    @property
+    def kind(self):
+        return self.queue.kind
+
+    def run(self, ops):
+        self.runs.append(list(ops))
+        return self.queue.run(ops)
+
+
+def replicas_read(runs, model, n_replicas, region=1 << 20):
+    """Replicas that served at least one valid read of `runs`: a
+    replicated bdev routes a read to replica (offset // region) % n."""
+    return {(op[1] // region) % n_replicas
+            for ops in runs for op in ops
+            if op[0] == "read" and model.valid(op)}
+
+
+def stripe_layout(data, n_children, stripe):
+    """The bytes each child of a striped bdev must hold when the bdev
+    holds `data`: child c holds, in ascending order, the stripe units u
+    (unit u is data[u * stripe:(u + 1) * stripe]) with u % n == c."""
+    assert len(data) % (n_children * stripe) == 0
+    units = [bytes(data[at:at + stripe])
+             for at in range(0, len(data), stripe)]
+    return [b"".join(units[child::n_children])
+            for child in range(n_children)]
+
+
 def scenario_tile_edges(q, model, seed):
     """Writes, fills and reads at every edge length in ONE run, at
     offsets that are block- but not tile-aligned; then read everything
@@ -302,3 +339,72 @@ def scenario_mixed_batch(q, model, seed):
     run_checked(q, model, readback(accepted) + guard_reads(accepted)
                 + [odd_target, zero_target])
     return sum(op_tiles(op) for op in accepted)
+
+
+def stripe_boundary_shapes(size, stripe, n_children, seed):
+    """[(offset, length)] placed relative to stripe boundaries.
+
+    The bdev is cut into zones of (2n + 4) stripe units. Zone 0 and the
+    last zone stay free for the end cases; up to four zones in between
+    (the first, the last and two seeded picks) each hold
+      * one block on each side of one boundary,
+      * exactly one unit,
+      * n + 2 pieces with ragged ends: every child, one of them twice.
+    The shapes of one zone do not touch (the first ends at or before
+    the unit the second starts with, the third starts half a unit or
+    more after it), and the third ends inside its zone."""
+    zone = (2 * n_children + 4) * stripe
+    middle = list(range(1, size // zone - 1))
+    assert middle, (
+        f"{size} bytes hold {size // zone} zones of {zone}: need three")
+    if len(middle) > 4:
+        inner = random.Random(seed).sample(middle[1:-1], 2)
+        middle = sorted([middle[0], middle[-1]] + inner)
+    shapes = []
+    for index in middle:
+        z = index * zone
+        shapes.append((z + stripe - 512, 1024))
+        shapes.append((z + 2 * stripe, stripe))
+        shapes.append((z + 4 * stripe - 512, n_children * stripe + 1024))
+        assert shapes[-1][0] + shapes[-1][1] <= z + zone
+    return shapes
+
+
+def scenario_stripe_boundaries(q, model, seed, stripe, n_children):
+    """Writes, fills and reads cut at stripe boundaries of a striped
+    bdev of `n_children` children (see stripe_boundary_shapes), the
+    first block of the bdev, and a request that ends on its last byte.
+    Every run holds all shapes, so the pieces of many parent requests
+    sit in the children's queues together."""
+    rng = random.Random(seed)
+    size = model.size
+    shapes = stripe_boundary_shapes(size, stripe, n_children, seed)
+    seeded = [("write", at, rng.randbytes(length)) for at, length in shapes]
+    run_checked(q, model, seeded)
+    run_checked(q, model, readback(seeded))
+
+    # Fills first and third: with a single zone both 0x00 and 0xFF are
+    # still used, and from two zones on every shape meets both kinds.
+    values = (0x00, 0xFF, 0xA5, 0x3C)
+    over = []
+    for i, (at, length) in enumerate(shapes):
+        if i % 2 == 0:
+            over.append(("fill", at, length, values[(i // 2) % len(values)]))
+        else:
+            over.append(("write", at, rng.randbytes(length)))
+    assert {0x00, 0xFF} <= {op[3] for op in over if op[0] == "fill"}
+    # End cases (zone 0 and the last zone are otherwise unused; the
+    # background there is zero, so neither stores zeros).
+    first = ("fill", 0, 512, 0x5A)
+    last = ("write", size - stripe - 512, rng.randbytes(stripe + 512))
+    over.insert(len(over) // 2, ("flush",))
+    over += [first, last]
+    run_checked(q, model, over)
+
+    crossing = ("read", size - 512, 1024)
+    final = readback(over) + guard_reads(over[:-2])
+    # The end cases have no block before, or after, them.
+    final += [("read", 512, 512), ("read", last[1] - 512, 512), crossing]
+    results = run_checked(q, model, final)
+    assert results[-1] == (STATUS_INVALID, None)
+    return sum(op_tiles(op) for op in over)

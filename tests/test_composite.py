@@ -1,5 +1,6 @@
 """Striped / replicated composite bdevs (CPU children; the xGMI
-peer-copy path is covered by gpu-marked tests in test_gpu.py)."""
+peer-copy path is covered by gpu-marked tests in test_gpu.py, queued
+I/O over HBM children by test_composite_gpu.py)."""
 
 import random
 
@@ -9,6 +10,7 @@ from oim_amd import _hipstore as hs
 from oim_amd import hipstore
 
 from fixtures import hipstored  # noqa: F401
+import io_model
 
 BLOCK = 512
 STRIPE = 4096  # small stripe so tests cross boundaries quickly
@@ -83,6 +85,101 @@ class TestReplicated:
         bdev.fill(0, 0xEE, 16 * BLOCK)
         for child in children:
             assert child.read(0, BLOCK) == b"\xee" * BLOCK
+
+
+class TestCompositeByteModel:
+    """Queued I/O (hs.IoQueue: every request of a run submitted before
+    the first poll) through striped, replicated and nested bdevs on
+    malloc children, byte for byte against tests/io_model.py. Besides
+    the round trip through the composite, every child is read directly
+    and compared with the content the layout puts there, which a
+    consistently wrong placement cannot pass. tests/test_composite_gpu.py
+    runs the same scenarios over the HBM engines."""
+
+    # (children, stripe): a single child, stripes below and above the
+    # 4 KiB tile and no multiple of it, and the two production sizes.
+    GEOMETRIES = [(1, 4096), (2, 512), (3, 1536), (3, 4096), (2, 65536),
+                  (2, 131072)]
+    MIB = 1 << 20
+
+    @staticmethod
+    def striped(n, stripe):
+        """About 4 MiB in all; a child is a multiple of 1536 and 4096."""
+        child_bytes = {1: 4 << 20, 2: 2 << 20, 3: 1536 << 10}[n]
+        children = make_children(n, child_bytes // BLOCK)
+        bdev = hs.create_striped_bdev(f"bm-s{n}-{stripe}", children, stripe)
+        queue = hs.IoQueue(bdev)
+        assert queue.kind == "cpu"
+        return children, bdev, queue, io_model.ByteModel(bdev.size_bytes)
+
+    @staticmethod
+    def check_striped(children, bdev, model, stripe):
+        assert bdev.read(0, bdev.size_bytes) == bytes(model.data)
+        want = io_model.stripe_layout(model.data, len(children), stripe)
+        for index, child in enumerate(children):
+            assert child.read(0, child.size_bytes) == want[index], (
+                f"child {index} does not hold its stripe units")
+
+    def test_stripe_layout_reference(self):
+        """The placement reference on a case small enough to write out."""
+        data = bytes(range(12))
+        assert io_model.stripe_layout(data, 3, 2) == [
+            bytes([0, 1, 6, 7]), bytes([2, 3, 8, 9]), bytes([4, 5, 10, 11])]
+        assert io_model.stripe_layout(data, 1, 4) == [data]
+        assert io_model.stripe_layout(data, 2, 3) == [
+            bytes([0, 1, 2, 6, 7, 8]), bytes([3, 4, 5, 9, 10, 11])]
+
+    @pytest.mark.parametrize("n,stripe", GEOMETRIES)
+    def test_striped_boundaries(self, n, stripe):
+        children, bdev, queue, model = self.striped(n, stripe)
+        io_model.scenario_stripe_boundaries(queue, model, 31, stripe, n)
+        self.check_striped(children, bdev, model, stripe)
+
+    @pytest.mark.parametrize("n,stripe", GEOMETRIES)
+    def test_striped_tile_edges(self, n, stripe):
+        children, bdev, queue, model = self.striped(n, stripe)
+        assert io_model.scenario_tile_edges(queue, model, seed=32) == 82
+        self.check_striped(children, bdev, model, stripe)
+
+    @pytest.mark.parametrize("n,stripe", [(3, 1536), (2, 65536)])
+    def test_striped_mixed_batch(self, n, stripe):
+        children, bdev, queue, model = self.striped(n, stripe)
+        io_model.scenario_mixed_batch(queue, model, seed=33)
+        self.check_striped(children, bdev, model, stripe)
+
+    @pytest.mark.parametrize("n", [2, 3])
+    def test_replicated(self, n):
+        children = make_children(n, 4 * self.MIB // BLOCK)
+        bdev = hs.create_replicated_bdev(f"bm-r{n}", children)
+        queue = io_model.RecordingQueue(hs.IoQueue(bdev))
+        assert queue.kind == "cpu"
+        model = io_model.ByteModel(bdev.size_bytes)
+        io_model.scenario_tile_edges(queue, model, seed=11)
+        io_model.scenario_mixed_batch(queue, model, seed=12)
+        # A read at offset o is served by replica (o // 1 MiB) % n: the
+        # reads of this test must have reached every one of them.
+        served = io_model.replicas_read(queue.runs, model, n)
+        assert served == set(range(n)), served
+        assert bdev.read(0, bdev.size_bytes) == bytes(model.data)
+        for index, child in enumerate(children):
+            assert child.read(0, child.size_bytes) == bytes(model.data), (
+                f"replica {index} differs from the model")
+
+    def test_nested(self):
+        """A 4 KiB stripe over two replicated pairs."""
+        leaves = [make_children(2, 2 * self.MIB // BLOCK) for _ in range(2)]
+        pairs = [hs.create_replicated_bdev(f"bm-n{i}", leaves[i])
+                 for i in range(2)]
+        bdev = hs.create_striped_bdev("bm-n", pairs, 4096)
+        queue = hs.IoQueue(bdev)
+        model = io_model.ByteModel(bdev.size_bytes)
+        assert io_model.scenario_tile_edges(queue, model, seed=34) == 82
+        assert bdev.read(0, bdev.size_bytes) == bytes(model.data)
+        want = io_model.stripe_layout(model.data, 2, 4096)
+        for pair in range(2):
+            for replica, leaf in enumerate(leaves[pair]):
+                assert leaf.read(0, leaf.size_bytes) == want[pair], (
+                    f"pair {pair} replica {replica}")
 
 
 class TestCompositeRpc:
