@@ -568,11 +568,17 @@ class VhostUserScsiDev {
       // Register guest memory with the GPU so the HBM engine's copy
       // kernels DMA guest<->HBM directly (SPDK requires DMA-able guest
       // memory for vhost the same way). Without this, the engine's
-      // hipHostGetDevicePointer on a guest address fails.
+      // hipHostGetDevicePointer on a guest address fails. Where the
+      // platform cannot pin memory it did not allocate (virtualized
+      // GPUs), the session's data goes through pinned bounce buffers.
       if (gpu_available()) {
         region.hip_registered =
             hipHostRegister(region.base, region.size,
                             hipHostRegisterMapped) == hipSuccess;
+        if (!region.hip_registered) {
+          (void)hipGetLastError();  // must not stick to the next launch
+          bounce_guest_io_ = true;
+        }
       }
       regions_.push_back(region);
     }
@@ -585,6 +591,7 @@ class VhostUserScsiDev {
       ::munmap(r.map, r.maplen);
     }
     regions_.clear();
+    bounce_guest_io_ = false;
   }
 
   // Guest-controlled addr/len: `gpa + len` can wrap UINT64_MAX, so the
@@ -876,6 +883,9 @@ class VhostUserScsiDev {
                     ChannelCache* channels,
                     std::shared_ptr<uint32_t> inflight) {
     Vring& ring = rings_[ring_index];
+    // The engine cannot DMA unregistered guest memory; the sync path
+    // bounces it through a pinned buffer.
+    if (bounce_guest_io_) return false;
     std::vector<Iov> out, in;
     if (!collect_iovs(ring, head, &out, &in)) return false;
     const bool blk = personality_ == Personality::kBlk;
@@ -1231,19 +1241,18 @@ class VhostUserScsiDev {
           offset % bdev->block_size() != 0 ||
           offset + bytes > bdev->size_bytes() || bytes > kMaxIoBytes) {
         status = kStatusIoErr;
-      } else if (iovs.size() == 1) {
+      } else if (iovs.size() == 1 && !bounce_guest_io_) {
         if (bdev_io(channels, bdev, is_write ? IoOp::kWrite : IoOp::kRead,
                     offset, iovs[0].base, bytes) != kIoOk) {
           status = kStatusIoErr;
         }
       } else {
-        uint8_t* bounce = static_cast<uint8_t*>(alloc_pinned(bytes));
+        uint8_t* bounce = worker_bounce();
         if (is_write) gather(bounce, iovs, bytes);
         int io_status =
             bdev_io(channels, bdev, is_write ? IoOp::kWrite : IoOp::kRead,
                     offset, bounce, bytes);
         if (io_status == kIoOk && !is_write) scatter(iovs, bounce, bytes);
-        free_pinned(bounce);
         if (io_status != kIoOk) status = kStatusIoErr;
       }
     } else {
@@ -1267,6 +1276,24 @@ class VhostUserScsiDev {
     auto ch = bdev->get_channel();
     (*cache)[bdev.get()] = {bdev, ch};  // pins the bdev alive with it
     return ch;
+  }
+
+  // Pinned staging buffer of the calling ring worker, kMaxIoBytes long
+  // (no command moves more). Allocated on first use and kept until the
+  // thread exits, after its channels are gone: a hipHostMalloc and
+  // hipHostFree per command measured 1.3 s a command while a resident
+  // service kernel was running (freeing waits for the device's
+  // streams, and that kernel only leaves its stream when it idles out).
+  static uint8_t* worker_bounce() {
+    struct Holder {
+      uint8_t* ptr = nullptr;
+      ~Holder() { free_pinned(ptr); }
+    };
+    thread_local Holder holder;
+    if (holder.ptr == nullptr) {
+      holder.ptr = static_cast<uint8_t*>(alloc_pinned(kMaxIoBytes));
+    }
+    return holder.ptr;
   }
 
   static int bdev_io(ChannelCache* cache, const BdevPtr& bdev, IoOp op,
@@ -1545,7 +1572,7 @@ class VhostUserScsiDev {
         if (bytes == 0) return 0;
         const std::vector<Iov>& iovs = is_write ? data_out : data_in;
         int status;
-        if (iovs.size() == 1 && iovs[0].len >= bytes) {
+        if (iovs.size() == 1 && iovs[0].len >= bytes && !bounce_guest_io_) {
           status = bdev_io(channels, bdev,
                            is_write ? IoOp::kWrite : IoOp::kRead,
                            lba * block, iovs[0].base, bytes);
@@ -1557,7 +1584,7 @@ class VhostUserScsiDev {
           // Pinned bounce: the HBM engine DMAs from host memory, so a
           // plain vector is not eligible. alloc_pinned falls back to
           // malloc on CPU-only daemons.
-          uint8_t* bounce = static_cast<uint8_t*>(alloc_pinned(bytes));
+          uint8_t* bounce = worker_bounce();
           if (is_write) gather(bounce, iovs, bytes);
           status = bdev_io(channels, bdev,
                            is_write ? IoOp::kWrite : IoOp::kRead,
@@ -1565,7 +1592,6 @@ class VhostUserScsiDev {
           if (!is_write && status == kIoOk) {
             scatter(iovs, bounce, bytes);
           }
-          free_pinned(bounce);
         }
         if (status != kIoOk) {
           resp->response = kRespFailure;
@@ -1599,6 +1625,9 @@ class VhostUserScsiDev {
   uint64_t negotiated_features_ = 0;
   uint64_t protocol_features_ = 0;
   std::vector<Region> regions_;
+  // A region could not be registered with the GPU: read/write data is
+  // staged through alloc_pinned buffers instead of DMA'd in place.
+  bool bounce_guest_io_ = false;
   Vring rings_[kMaxVrings];
 
 };
