@@ -69,6 +69,22 @@ asan: $(ASAN_OBJS)
 	mkdir -p bin
 	$(HIPCC) $(HIPFLAGS) -fsanitize=address $^ $(LDLIBS) -o bin/hipstored-asan
 
+# Stand-alone checks of the submit path's lock-free host pieces (pinned
+# range registry, sharded I/O statistics): host code only, built once
+# plain and once under ThreadSanitizer, and run. Needs no GPU.
+SUBMIT_TEST_SRCS := tests/native/submit_path_test.cpp native/src/bdev.cpp
+
+$(B)/submit_path_test: $(SUBMIT_TEST_SRCS) $(HDRS) | $(B)
+	$(HIPCC) $(CXXFLAGS) -pthread $(SUBMIT_TEST_SRCS) -o $@
+
+$(B)/submit_path_test_tsan: $(SUBMIT_TEST_SRCS) $(HDRS) | $(B)
+	$(HIPCC) $(CXXFLAGS) -O1 -g -Xarch_host -fsanitize=thread -pthread $(SUBMIT_TEST_SRCS) -o $@
+
+.PHONY: submit-path-test
+submit-path-test: $(B)/submit_path_test $(B)/submit_path_test_tsan
+	$(B)/submit_path_test
+	$(B)/submit_path_test_tsan
+
 clean:
 	rm -rf $(B) bin oim_amd/_hipstore*.so
 

@@ -43,6 +43,7 @@
 
 #include "gpu_internal.h"
 #include "hipstore/engine.h"
+#include "hipstore/pinned_ranges.h"
 
 namespace hipstore {
 
@@ -721,6 +722,16 @@ void* alloc_pinned(size_t bytes) {
   if (!gpu_available()) return malloc(bytes);
   void* p = nullptr;
   HIP_CHECK(hipHostMalloc(&p, bytes, hipHostMallocMapped));
+  // Recorded so that the engines translate I/O buffers inside it
+  // without a runtime call (pinned_ranges.h). A buffer whose device
+  // view cannot be had is simply not recorded: it takes the engines'
+  // fallback, as before.
+  void* dev = nullptr;
+  if (hipHostGetDevicePointer(&dev, p, 0) == hipSuccess) {
+    pinned_ranges().add(p, bytes, dev);
+  } else {
+    (void)hipGetLastError();
+  }
   return p;
 }
 
@@ -730,6 +741,9 @@ void free_pinned(void* ptr) {
     free(ptr);
     return;
   }
+  // Before the free: afterwards the allocator may hand the address to
+  // another thread, whose record this would remove.
+  pinned_ranges().remove(ptr);
   (void)hipHostFree(ptr);
 }
 
@@ -773,14 +787,25 @@ inline HbmChannelBase* hbm_channel(IoChannel* ch) {
 // The caller's buffer may be pinned (device-visible) or pageable.
 // Pinned path: translate; pageable would need a bounce buffer — the
 // daemon and bench always use alloc_pinned, so reject pageable here.
-uint8_t* buf_device(uint8_t* host) {
+void* buf_device_runtime(void* host) {
   void* dev = nullptr;
   hipError_t err = hipHostGetDevicePointer(&dev, host, 0);
   if (err != hipSuccess) {
     throw std::runtime_error(
         "hipstore: I/O buffer is not pinned host memory (use alloc_pinned)");
   }
-  return static_cast<uint8_t*>(dev);
+  return dev;
+}
+
+// The `bytes`-long tile buffer at `host`, as the GPU addresses it.
+// Buffers inside a recorded pinned range (alloc_pinned, registered
+// guest memory) translate from the channel's remembered range with no
+// runtime call: hipHostGetDevicePointer takes the runtime's lock, once
+// per tile, on every submitter thread. Memory the caller pinned itself
+// still asks the runtime.
+uint8_t* buf_device(PinnedRangeCache& cache, uint8_t* host, uint32_t bytes) {
+  return static_cast<uint8_t*>(
+      pinned_ranges().translate(cache, host, bytes, buf_device_runtime));
 }
 
 // Requests are split into <=4 KiB tiles, one descriptor each.
@@ -791,12 +816,12 @@ inline uint32_t tile_count(uint64_t length) {
 // Descriptor for the `bytes`-long tile at byte `done` of a read, write
 // or fill request against the backing store at `base`.
 void fill_desc(BlockDesc& d, const IoRequest& req, uint8_t* base,
-               uint64_t done, uint32_t bytes) {
+               uint64_t done, uint32_t bytes, PinnedRangeCache& cache) {
   if (req.op == IoOp::kRead) {
     d.src = base + req.offset + done;
-    d.dst = buf_device(static_cast<uint8_t*>(req.buffer) + done);
+    d.dst = buf_device(cache, static_cast<uint8_t*>(req.buffer) + done, bytes);
   } else if (req.op == IoOp::kWrite) {
-    d.src = buf_device(static_cast<uint8_t*>(req.buffer) + done);
+    d.src = buf_device(cache, static_cast<uint8_t*>(req.buffer) + done, bytes);
     d.dst = base + req.offset + done;
   } else {  // kFill
     d.src = nullptr;
@@ -935,7 +960,7 @@ class HbmChannel : public HbmChannelBase {
     while (done < req.length) {
       const uint32_t bytes = static_cast<uint32_t>(
           std::min<uint64_t>(kTileBytes, req.length - done));
-      fill_desc(ring_[*slot], req, base_, done, bytes);
+      fill_desc(ring_[*slot], req, base_, done, bytes, buf_cache_);
       ++*slot;
       done += bytes;
     }
@@ -958,6 +983,7 @@ class HbmChannel : public HbmChannelBase {
   hipStream_t stream_ = nullptr;
   BlockDesc* ring_ = nullptr;      // pinned host
   BlockDesc* ring_dev_ = nullptr;  // GPU view of the ring
+  PinnedRangeCache buf_cache_;     // pinned range the last buffer was in
   uint32_t ring_head_ = 0;
   uint32_t used_slots_ = 0;
   std::vector<PendingIo> pending_;
@@ -985,8 +1011,10 @@ class ServiceRingChannel : public HbmChannelBase {
       flushes_.push_back({tail_, std::move(req.on_complete)});
       return;
     }
+    // Straight into the ring when nothing waits ahead of it (the deque
+    // allocates and frees a block every few requests otherwise).
+    if (pending_.empty() && issue(req)) return;
     pending_.push_back(std::move(req));
-    drain_pending();
   }
 
   int poll() override {
@@ -1013,8 +1041,13 @@ class ServiceRingChannel : public HbmChannelBase {
       desc_io_[completed_ % kRing] = nullptr;
       ++completed_;
       if (state != nullptr && --state->remaining == 0) {
-        if (state->cb) state->cb(state->status);
-        delete state;
+        // Back to the pool first: the callback may resubmit and take
+        // it again.
+        IoCompletion cb = std::move(state->cb);
+        const int status = state->status;
+        state->cb = nullptr;
+        free_states_.push_back(state);
+        if (cb) cb(status);
         ++completed;
       }
     }
@@ -1085,15 +1118,20 @@ class ServiceRingChannel : public HbmChannelBase {
   // Unfired completion callbacks (wedge teardown, undrained multi-tile
   // IOs): delete, never call, so their captures are released without
   // touching torn state.
+  // The states live in the channel's pool, so this drops the captures
+  // of those still in flight and forgets which descriptors named them.
   void delete_unfired() {
-    std::set<IoState*> leftovers(desc_io_.begin(), desc_io_.end());
-    for (IoState* state : leftovers) delete state;
+    std::fill(desc_io_.begin(), desc_io_.end(), nullptr);
+    for (IoState& state : states_) state.cb = nullptr;
   }
 
   BlockDesc* sq_ = nullptr;
   volatile unsigned long long* sq_tail_ = nullptr;
   volatile unsigned long long* cq_ = nullptr;
-  uint64_t tail_ = 0;
+  // What the owning thread writes per I/O starts on a cache line of its
+  // own, and the alignment rounds the object up to whole lines: no
+  // other thread's channel, and nothing else on the heap, shares one.
+  alignas(64) uint64_t tail_ = 0;
   uint64_t completed_ = 0;
   std::chrono::steady_clock::time_point last_progress_{};
 
@@ -1109,31 +1147,67 @@ class ServiceRingChannel : public HbmChannelBase {
     return tail_ - completed_ + tiles <= kRing;
   }
 
-  void drain_pending() {
-    while (!pending_.empty()) {
-      IoRequest& req = pending_.front();
-      const uint32_t tiles = tile_count(req.length);
-      if (!has_capacity(tiles)) return;
-      auto* state = new IoState{std::move(req.on_complete), tiles, kIoOk};
-      uint64_t done = 0;
-      uint64_t t = tail_;
+  // A request's state from the channel's pool. At most kRing are in
+  // use at once (each holds a descriptor or more), and the pool grows
+  // to the most the channel ever had in flight, so a running queue does
+  // no heap work per request. A deque: the states stay where they are.
+  IoState* take_state() {
+    if (free_states_.empty()) {
+      states_.emplace_back();
+      return &states_.back();
+    }
+    IoState* state = free_states_.back();
+    free_states_.pop_back();
+    return state;
+  }
+
+  // Write the request's descriptors and publish them; false when the
+  // ring has no room for all of them yet.
+  bool issue(IoRequest& req) {
+    const uint32_t tiles = tile_count(req.length);
+    if (!has_capacity(tiles)) return false;
+    IoState* state = take_state();
+    state->cb = std::move(req.on_complete);
+    state->remaining = tiles;
+    state->status = kIoOk;
+    uint64_t done = 0;
+    uint64_t t = tail_;
+    try {
       while (done < req.length) {
         const uint32_t bytes = static_cast<uint32_t>(
             std::min<uint64_t>(kTileBytes, req.length - done));
-        fill_desc(sq_[t % kRing], req, base_, done, bytes);
+        fill_desc(sq_[t % kRing], req, base_, done, bytes, buf_cache_);
         desc_io_[t % kRing] = state;
         ++t;
         done += bytes;
       }
-      tail_ = t;
-      // Publish: descriptors before the tail, release order.
-      __atomic_store_n(const_cast<unsigned long long*>(sq_tail_), tail_,
-                       __ATOMIC_RELEASE);
+    } catch (...) {
+      // An unpinned buffer: nothing was published. Hand the callback
+      // back with the request and forget the descriptors written.
+      for (uint64_t u = tail_; u < t; ++u) desc_io_[u % kRing] = nullptr;
+      req.on_complete = std::move(state->cb);
+      state->cb = nullptr;
+      free_states_.push_back(state);
+      throw;
+    }
+    tail_ = t;
+    // Publish: descriptors before the tail, release order.
+    __atomic_store_n(const_cast<unsigned long long*>(sq_tail_), tail_,
+                     __ATOMIC_RELEASE);
+    return true;
+  }
+
+  void drain_pending() {
+    while (!pending_.empty()) {
+      if (!issue(pending_.front())) return;
       pending_.pop_front();
     }
   }
 
   uint8_t* base_;
+  PinnedRangeCache buf_cache_;  // pinned range the last buffer was in
+  std::deque<IoState> states_;
+  std::vector<IoState*> free_states_;
   std::vector<IoState*> desc_io_;
   std::deque<IoRequest> pending_;
   std::deque<std::pair<uint64_t, IoCompletion>> flushes_;
@@ -2051,10 +2125,13 @@ void maybe_pin_thread(int queue_index) {
   (void)pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
 }
 
-struct PerfQueueStats {
+// One per queue thread, in a vector: whole cache lines each, so that
+// one queue's counters never share a line with its neighbour's.
+struct alignas(64) PerfQueueStats {
   uint64_t ios = 0;
   LatHist lat;
 };
+static_assert(sizeof(PerfQueueStats) % 64 == 0, "whole cache lines");
 
 // One benchmark queue, shared by run_bdevperf and PerfSession:
 // queue_depth buffer slots on one channel, each slot resubmitting a
@@ -2287,6 +2364,8 @@ struct PerfSession::Impl {
     uint64_t done_epoch = 0;
     bool failed = false;
   };
+  static_assert(alignof(QueueStats) == 64 && sizeof(QueueStats) % 64 == 0,
+                "queue q's histogram and queue q+1's count on one line");
   std::vector<QueueStats> stats;
   std::vector<std::thread> threads;
 

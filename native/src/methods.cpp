@@ -834,14 +834,14 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
     const std::string name = p.get_string("name");
     JsonArray bdevs;
     auto one = [](const BdevPtr& bdev) {
-      auto& st = bdev->iostat();
+      const Bdev::IoStat st = bdev->iostat();
       JsonObject o;
       o["name"] = Json(bdev->name());
-      o["num_read_ops"] = Json(static_cast<int64_t>(st.num_read_ops.load()));
-      o["num_write_ops"] = Json(static_cast<int64_t>(st.num_write_ops.load()));
-      o["num_unmap_ops"] = Json(static_cast<int64_t>(st.num_unmap_ops.load()));
-      o["bytes_read"] = Json(static_cast<int64_t>(st.bytes_read.load()));
-      o["bytes_written"] = Json(static_cast<int64_t>(st.bytes_written.load()));
+      o["num_read_ops"] = Json(static_cast<int64_t>(st.num_read_ops));
+      o["num_write_ops"] = Json(static_cast<int64_t>(st.num_write_ops));
+      o["num_unmap_ops"] = Json(static_cast<int64_t>(st.num_unmap_ops));
+      o["bytes_read"] = Json(static_cast<int64_t>(st.bytes_read));
+      o["bytes_written"] = Json(static_cast<int64_t>(st.bytes_written));
       return Json(std::move(o));
     };
     if (!name.empty()) {

@@ -229,6 +229,18 @@ PYBIND11_MODULE(_hipstore, m) {
              return b.resize(num_blocks);
            },
            py::arg("num_blocks"))
+      .def("iostat",
+           [](const hipstore::Bdev& b) {
+             // The get_bdevs_iostat RPC's counters, by the same names.
+             const hipstore::Bdev::IoStat st = b.iostat();
+             py::dict d;
+             d["num_read_ops"] = st.num_read_ops;
+             d["num_write_ops"] = st.num_write_ops;
+             d["num_unmap_ops"] = st.num_unmap_ops;
+             d["bytes_read"] = st.bytes_read;
+             d["bytes_written"] = st.bytes_written;
+             return d;
+           })
       .def("read", &bdev_read_py, py::arg("offset"), py::arg("length"),
            py::call_guard<py::gil_scoped_release>())
       .def("write", &bdev_write_py, py::arg("offset"), py::arg("data"))

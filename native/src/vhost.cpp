@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "hipstore/engine.h"
+#include "hipstore/pinned_ranges.h"
 
 namespace hipstore {
 namespace {
@@ -578,6 +579,15 @@ class VhostUserScsiDev {
         if (!region.hip_registered) {
           (void)hipGetLastError();  // must not stick to the next launch
           bounce_guest_io_ = true;
+        } else {
+          // Let the engines translate guest buffers without a runtime
+          // call per tile (pinned_ranges.h).
+          void* dev = nullptr;
+          if (hipHostGetDevicePointer(&dev, region.base, 0) == hipSuccess) {
+            pinned_ranges().add(region.base, region.size, dev);
+          } else {
+            (void)hipGetLastError();
+          }
         }
       }
       regions_.push_back(region);
@@ -587,7 +597,10 @@ class VhostUserScsiDev {
 
   void unmap_regions() {
     for (const Region& r : regions_) {
-      if (r.hip_registered) (void)hipHostUnregister(r.base);
+      if (r.hip_registered) {
+        pinned_ranges().remove(r.base);
+        (void)hipHostUnregister(r.base);
+      }
       ::munmap(r.map, r.maplen);
     }
     regions_.clear();

@@ -11,8 +11,15 @@ HBM bdev and prints one JSON line per shape:
     q1_qd64_w4 / w8 / w16    1 queue, QD 64, HIPSTORE_PERSISTENT_WORKERS
                              4 / 8 / 16: IOPS that scale with the
                              workers mean the queue is worker-bound
+    q{1,2,4,8,14}_qd32_512, q{1,2,4,8,14}_qd32_4k
+                             the thread ladder (--ladder threads): the
+                             same queue on 1 to 14 host threads. 512 B
+                             keeps the link idle, so IOPS per thread
+                             that fall with the thread count mean the
+                             threads share something on the host
 
-    python tools/queue_ladder.py [--steps 7] [--warmup 2] [--shapes NAME ...]
+    python tools/queue_ladder.py [--steps 7] [--warmup 2]
+                                 [--shapes NAME ... | --ladder threads]
 
 Every shape runs in a process of its own (the engine's knobs are read
 from the environment, some of them once per process), which sets
@@ -20,9 +27,13 @@ GPU_MAX_HW_QUEUES and HIPSTORE_AFFINITY_BASE the way bench.py does.
 HIPSTORE_BATCH_TILES and the other engine knobs are passed through from
 the caller's environment and echoed in the line. Each line holds the
 median and the min-max of the steps' IOPS, the same as GB/s, and the
-median of the steps' p50 and p99 latency. Measurement only; needs a GPU:
-there is no fallback."""
+median of the steps' p50 and p99 latency, the median IOPS divided by the
+queue threads, and the context switches of the process's threads over the
+timed steps (from /proc/self/task/*/status): queue threads spin, so a
+voluntary switch is a thread put to sleep on a lock. Measurement only;
+needs a GPU: there is no fallback."""
 import argparse
+import glob
 import json
 import os
 import statistics
@@ -38,7 +49,14 @@ SHAPES = {
     "q1_qd16": (1, 16, 4096, 65536, None),
     "q1_qd32": (1, 32, 4096, 65536, None),
     "q1_qd64": (1, 64, 4096, 65536, None),
+    "q1_qd32_512": (1, 32, 512, 32768, None),
+    "q2_qd32_512": (2, 32, 512, 65536, None),
+    "q4_qd32_512": (4, 32, 512, 131072, None),
+    "q8_qd32_512": (8, 32, 512, 262144, None),
+    "q1_qd32_4k": (1, 32, 4096, 65536, None),
+    "q2_qd32_4k": (2, 32, 4096, 65536, None),
     "q4_qd32_4k": (4, 32, 4096, 131072, None),
+    "q8_qd32_4k": (8, 32, 4096, 131072, None),
     "q4_qd32_64k": (4, 32, 65536, 16384, None),
     "q14_qd32_512": (14, 32, 512, 262144, None),
     "q14_qd32_4k": (14, 32, 4096, 131072, None),
@@ -46,6 +64,27 @@ SHAPES = {
     "q1_qd64_w8": (1, 64, 4096, 65536, 8),
     "q1_qd64_w16": (1, 64, 4096, 65536, 16),
 }
+
+LADDERS = {
+    "threads": [f"q{q}_qd32_{size}" for size in ("512", "4k")
+                for q in (1, 2, 4, 8, 14)],
+}
+
+
+def context_switches():
+    """(voluntary, involuntary) summed over the threads alive now."""
+    totals = [0, 0]
+    for path in glob.glob("/proc/self/task/*/status"):
+        try:
+            with open(path) as f:
+                for line in f:
+                    if line.startswith("voluntary_ctxt_switches"):
+                        totals[0] += int(line.split()[1])
+                    elif line.startswith("nonvoluntary_ctxt_switches"):
+                        totals[1] += int(line.split()[1])
+        except OSError:
+            pass    # a thread that ended meanwhile
+    return totals
 
 
 def spread(values, digits=0):
@@ -72,7 +111,9 @@ def run_shape(name, steps, warmup):
     session = hs.PerfSession(bdev, "randread", io_size, depth, queues)
     for _ in range(warmup):
         session.step(step_ios)
+    before = context_switches()
     results = [session.step(step_ios) for _ in range(steps)]
+    after = context_switches()
     iops = [r["iops"] for r in results]
     print(json.dumps({
         "shape": name, "queues": queues, "queue_depth": depth,
@@ -80,6 +121,9 @@ def run_shape(name, steps, warmup):
         "workers": os.environ.get("HIPSTORE_PERSISTENT_WORKERS", "16"),
         "batch_tiles": os.environ.get("HIPSTORE_BATCH_TILES", "default"),
         "iops": spread(iops),
+        "iops_per_thread": round(statistics.median(iops) / queues),
+        "ctx_switches": {"voluntary": after[0] - before[0],
+                         "involuntary": after[1] - before[1]},
         "gb_per_s": spread([v * io_size / 1e9 for v in iops], 2),
         "p50_us": round(statistics.median(r["lat_p50_us"]
                                           for r in results), 2),
@@ -94,6 +138,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shapes", nargs="+", choices=list(SHAPES),
                     default=list(SHAPES))
+    ap.add_argument("--ladder", choices=list(LADDERS),
+                    help="run the shapes of a named ladder instead")
     ap.add_argument("--child", choices=list(SHAPES), help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.steps < 3:
@@ -102,7 +148,7 @@ def main():
         run_shape(args.child, args.steps, args.warmup)
         return 0
     status = 0
-    for name in args.shapes:
+    for name in (LADDERS[args.ladder] if args.ladder else args.shapes):
         env = dict(os.environ)
         workers = SHAPES[name][4]
         if workers is not None:
