@@ -24,7 +24,8 @@ CORE_OBJS := $(B)/json.o $(B)/bdev.o $(B)/crc32c.o $(B)/rpc_server.o \
              $(B)/methods.o $(B)/nbd.o $(B)/ublk.o $(B)/composite.o $(B)/vhost.o $(B)/vhost_master.o \
              $(B)/nvmf_common.o $(B)/nvmf_target.o $(B)/nvmf_initiator.o \
              $(B)/rados_client.o $(B)/rados_cluster.o $(B)/checked_file.o $(B)/delta.o \
-             $(B)/fingerprint.o $(B)/gpu.o $(B)/bulk_ops.o
+             $(B)/fingerprint.o $(B)/gpu.o $(B)/bulk_ops.o \
+             $(B)/parity.o $(B)/parity_ops.o
 
 .PHONY: all clean
 all: oim_amd/_hipstore$(EXT_SUFFIX) bin/hipstored
@@ -37,6 +38,9 @@ $(B)/%.o: native/src/%.cpp $(HDRS) | $(B)
 
 $(B)/%.o: native/src/%.hip $(HIP_HDRS) | $(B)
 	$(HIPCC) $(CXXFLAGS) $(HIPFLAGS) -c $< -o $@
+
+# parity_ops.hip does not launch gpu_internal.h's k_copy_range.
+$(B)/parity_ops.o $(B)/asan/parity_ops.o: HIPFLAGS += -Wno-unused-function
 
 $(B)/pybind.o: native/src/pybind.cpp $(HDRS) | $(B)
 	$(HIPCC) $(CXXFLAGS) -fvisibility=hidden -I$(PY_INC) -I$(PYBIND_INC) -c $< -o $@
@@ -84,6 +88,18 @@ $(B)/submit_path_test_tsan: $(SUBMIT_TEST_SRCS) $(HDRS) | $(B)
 submit-path-test: $(B)/submit_path_test $(B)/submit_path_test_tsan
 	$(B)/submit_path_test
 	$(B)/submit_path_test_tsan
+
+# Stand-alone check of the parity host code (GF(2^8) tables, rebuild
+# coefficients, the generic path on malloc bdevs) under AddressSanitizer:
+# host code only, needs no GPU.
+PARITY_TEST_SRCS := tests/native/parity_test.cpp native/src/parity.cpp native/src/bdev.cpp
+
+$(B)/parity_test_asan: $(PARITY_TEST_SRCS) $(HDRS) | $(B)
+	$(HIPCC) $(CXXFLAGS) $(subst -fsanitize,-Xarch_host -fsanitize,$(ASAN_FLAGS)) -pthread $(PARITY_TEST_SRCS) -o $@
+
+.PHONY: parity-test
+parity-test: $(B)/parity_test_asan
+	$(B)/parity_test_asan
 
 clean:
 	rm -rf $(B) bin oim_amd/_hipstore*.so

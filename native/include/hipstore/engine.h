@@ -2,7 +2,7 @@
 // helpers, the sync wrappers, IoQueue and bdevperf are implemented in
 // gpu.hip; hbm_copy_sync and the bdev_diff / copy_marked / pack_marked /
 // unpack_marked / fingerprint calls (and marked_copy_probe) in
-// bulk_ops.hip.
+// bulk_ops.hip. P+Q parity across bdevs has its own header, parity.h.
 //
 // MI355X-native replacement for the reference's SPDK copy engine +
 // malloc bdev pair (reference lib/copy/copy_engine.c,

@@ -334,55 +334,7 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_fingerprint_granules(
 }
 
 // --- host helpers shared by every call below -------------------------------
-
-// A one-shot stream: device selected, own non-blocking stream created
-// (never a device-wide sync: it would block on live persistent service
-// kernels), and the hipErrorNotReady that polling elsewhere on this
-// thread leaves behind cleared, so that only a failure of the caller's
-// own work can fail the call. Synchronised, then destroyed, on every
-// way out of the scope.
-struct ScopedStream {
-  hipStream_t stream = nullptr;
-
-  explicit ScopedStream(int device) {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    (void)hipGetLastError();
-  }
-  ~ScopedStream() {
-    (void)hipStreamSynchronize(stream);
-    (void)hipStreamDestroy(stream);
-  }
-  ScopedStream(const ScopedStream&) = delete;
-  ScopedStream& operator=(const ScopedStream&) = delete;
-};
-
-// Pinned host buffer that grows on demand and keeps what it has. It
-// frees only in its destructor: hipHostFree waits for the device to go
-// idle, which stalls behind resident service kernels (see
-// IoQueue::run), so the per-thread buffers below free nothing per call.
-template <typename T>
-struct PinnedBuf {
-  T* ptr = nullptr;
-  uint64_t capacity = 0;  // elements
-
-  PinnedBuf() = default;
-  ~PinnedBuf() { free_pinned(ptr); }
-  PinnedBuf(const PinnedBuf&) = delete;
-  PinnedBuf& operator=(const PinnedBuf&) = delete;
-
-  T* reserve(uint64_t n) {
-    if (n > capacity) {
-      free_pinned(ptr);
-      ptr = nullptr;
-      capacity = 0;
-      ptr = static_cast<T*>(alloc_pinned(n * sizeof(T)));
-      if (ptr == nullptr) throw std::runtime_error("bulk: out of memory");
-      capacity = n;
-    }
-    return ptr;
-  }
-};
+// (ScopedStream, PinnedBuf and run_granule_kernel are in gpu_internal.h.)
 
 constexpr uint64_t kDiffHostChunk = 1ull << 20;  // generic-path read size cap
 // 256 MiB of bitmap; keeps the pinned buffer and the host fold bounded.
@@ -573,21 +525,6 @@ int granule_kernel_device(Bdev* a, Bdev* b) {
   (void)hipGetLastError();  // "already enabled" must not stick
   if (err != hipSuccess && err != hipErrorPeerAccessAlreadyEnabled) return -1;
   return a_dev;
-}
-
-// Own stream, one launch, synchronise: only a failure of this launch
-// (the stream starts with the last error cleared) may fail the call.
-template <typename Launch>
-int run_granule_kernel(int device, Launch launch) {
-  try {
-    ScopedStream ss(device);
-    launch(ss.stream);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(ss.stream);
-    return err == hipSuccess ? kIoOk : kIoFailed;
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
 }
 
 uint32_t granule_grid(uint64_t n_granules) {

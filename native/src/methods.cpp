@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <numeric>
 
 #include "hipstore/bdev.h"
 #include "hipstore/composite.h"
@@ -19,6 +20,7 @@
 #include "hipstore/json.h"
 #include "hipstore/nbd.h"
 #include "hipstore/nvmf.h"
+#include "hipstore/parity.h"
 #include "hipstore/rados.h"
 #include "hipstore/ublk.h"
 #include "hipstore/rpc.h"
@@ -1075,6 +1077,153 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(r.granule));
         o["replicas"] = Json(std::move(replicas));
+        return Json(std::move(o));
+      });
+
+  // --- P+Q parity across volumes (native extensions) -----------------------
+  // Shared params: "data" (bdev names; the order is the member index),
+  // "p" / "q" (either may be absent), "offset" and "length" common to
+  // all members, length defaulting to the whole of the shortest member
+  // in units of `unit`. kIoInvalid is -32602 and the message names the
+  // rule; everything else is -32603.
+  struct ParityParams {
+    std::vector<BdevPtr> hold;  // keeps the members alive for the call
+    std::vector<ParityMember> data;
+    ParityMember p;
+    ParityMember q;
+    uint64_t length = 0;
+  };
+  auto parity_params = [&manager, uint_param](const char* method,
+                                              const Json& p, uint64_t unit) {
+    ParityParams out;
+    const uint64_t offset = uint_param(p, "offset", 0);
+    auto member = [&](const std::string& name) {
+      BdevPtr bdev = manager.find(name);
+      if (!bdev) not_found("bdev " + name);
+      out.hold.push_back(bdev);
+      return ParityMember{bdev.get(), offset};
+    };
+    const Json* data = p.get("data");
+    if (data == nullptr || !data->is_array()) {
+      throw RpcError{kInvalidParams,
+                     std::string(method) + ": data must be a list of bdev names"};
+    }
+    for (const Json& name : data->as_array()) {
+      if (!name.is_string()) {
+        throw RpcError{kInvalidParams,
+                       std::string(method) +
+                           ": data must be a list of bdev names"};
+      }
+      out.data.push_back(member(name.as_string()));
+    }
+    if (p.has("p")) out.p = member(p.get_string("p"));
+    if (p.has("q")) out.q = member(p.get_string("q"));
+    if (p.has("length")) {
+      out.length = uint_param(p, "length", 0);
+    } else if (!out.data.empty()) {
+      // As the Python binding: whole blocks that are multiples of 16.
+      if (unit == 0) {
+        unit = std::lcm<uint64_t>(out.data[0].bdev->block_size(), 16);
+      }
+      out.length = parity_common_length(out.data, out.p, out.q, unit);
+    }
+    return out;
+  };
+  auto parity_error = [](const char* method, int status,
+                         const ParityReport& report) {
+    return RpcError{status == kIoInvalid ? kInvalidParams : kInternalError,
+                    std::string(method) + ": " + report.error};
+  };
+
+  server->register_method(
+      "bdev_parity_encode", [parity_params, parity_error](const Json& p) {
+        // P and / or Q of the data volumes, written to the p / q volumes
+        // (k_parity_encode for HBM sets).
+        const ParityParams a = parity_params("bdev_parity_encode", p, 0);
+        ParityReport report;
+        const int status =
+            bdev_parity_encode_sync(a.data, a.p, a.q, a.length, &report);
+        if (status != kIoOk) {
+          throw parity_error("bdev_parity_encode", status, report);
+        }
+        JsonObject o;
+        o["length"] = Json(static_cast<int64_t>(a.length));
+        o["on_gpu"] = Json(report.on_gpu);
+        return Json(std::move(o));
+      });
+
+  server->register_method(
+      "bdev_parity_scrub",
+      [parity_params, parity_error, uint_param, max_report_param,
+       indices_to_json](const Json& p) {
+        // Recompute the parity and compare with what is stored; only
+        // reads, so claimed volumes are fine.
+        uint64_t granule = uint_param(p, "granule", 0);
+        if (granule > UINT32_MAX) {
+          throw RpcError{kInvalidParams, "granule too large"};
+        }
+        ParityParams a = parity_params("bdev_parity_scrub", p, granule);
+        if (granule == 0 && !a.data.empty()) {
+          granule = a.data[0].bdev->block_size();
+        }
+        ParityReport report;
+        ParityCheck check;
+        const int status = bdev_parity_check_sync(
+            a.data, a.p, a.q, a.length, static_cast<uint32_t>(granule),
+            max_report_param(p), &check, &report);
+        if (status != kIoOk) {
+          throw parity_error("bdev_parity_scrub", status, report);
+        }
+        auto stats_json = [&](const DiffStats& stats) {
+          JsonObject o;
+          o["granules"] = Json(static_cast<int64_t>(stats.granules));
+          o["mismatched"] = Json(static_cast<int64_t>(stats.mismatched));
+          o["first_mismatches"] = indices_to_json(stats.first_mismatches);
+          return Json(std::move(o));
+        };
+        JsonObject o;
+        o["granule"] = Json(static_cast<int64_t>(granule));
+        o["on_gpu"] = Json(report.on_gpu);
+        if (a.p.bdev != nullptr) o["p"] = stats_json(check.p);
+        if (a.q.bdev != nullptr) o["q"] = stats_json(check.q);
+        return Json(std::move(o));
+      });
+
+  server->register_method(
+      "bdev_parity_rebuild", [parity_params, parity_error](const Json& p) {
+        // Rewrite the members named by "lost" (data indices, "p", "q")
+        // from the others; offline only.
+        const ParityParams a = parity_params("bdev_parity_rebuild", p, 0);
+        const Json* lost = p.get("lost");
+        if (lost == nullptr || !lost->is_array()) {
+          throw RpcError{kInvalidParams,
+                         "bdev_parity_rebuild: lost must be a list of data "
+                         "indices, \"p\" or \"q\""};
+        }
+        std::vector<int> lost_ids;
+        for (const Json& item : lost->as_array()) {
+          if (item.is_string() && item.as_string() == "p") {
+            lost_ids.push_back(kParityLostP);
+          } else if (item.is_string() && item.as_string() == "q") {
+            lost_ids.push_back(kParityLostQ);
+          } else if (item.is_int() && item.as_int() >= 0 &&
+                     item.as_int() < INT32_MAX) {
+            lost_ids.push_back(static_cast<int>(item.as_int()));
+          } else {
+            throw RpcError{kInvalidParams,
+                           "bdev_parity_rebuild: lost must be a list of data "
+                           "indices, \"p\" or \"q\""};
+          }
+        }
+        ParityReport report;
+        const int status = bdev_parity_rebuild_sync(a.data, a.p, a.q, a.length,
+                                                    lost_ids, &report);
+        if (status != kIoOk) {
+          throw parity_error("bdev_parity_rebuild", status, report);
+        }
+        JsonObject o;
+        o["length"] = Json(static_cast<int64_t>(a.length));
+        o["on_gpu"] = Json(report.on_gpu);
         return Json(std::move(o));
       });
 

@@ -10,6 +10,7 @@
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <numeric>
 #include <optional>
 #include <stdexcept>
 
@@ -20,6 +21,7 @@
 #include "hipstore/engine.h"
 #include "hipstore/fingerprint.h"
 #include "hipstore/nvmf.h"
+#include "hipstore/parity.h"
 #include "hipstore/rados.h"
 #include "hipstore/vhost_master.h"
 
@@ -206,6 +208,68 @@ void delta_call(const char* what, Call call) {
                            std::to_string(status) + ")";
   if (status == kIoInvalid) throw std::invalid_argument(text);
   throw std::runtime_error(text);
+}
+
+// The member set of the parity bindings. `offsets` empty = all zero;
+// length 0 = what is left of the shortest member, in whole `unit`s.
+struct ParityArgs {
+  std::vector<ParityMember> data;
+  ParityMember p;
+  ParityMember q;
+  uint64_t length = 0;
+};
+
+ParityArgs parity_args(const std::vector<BdevPtr>& data, const BdevPtr& p,
+                       const BdevPtr& q,
+                       const std::vector<uint64_t>& data_offsets,
+                       uint64_t p_offset, uint64_t q_offset, uint64_t length,
+                       uint64_t unit) {
+  if (!data_offsets.empty() && data_offsets.size() != data.size()) {
+    throw std::invalid_argument("parity: one offset per data member");
+  }
+  ParityArgs args;
+  for (size_t i = 0; i < data.size(); ++i) {
+    if (!data[i]) throw std::invalid_argument("parity: data member is None");
+    args.data.push_back(
+        {data[i].get(), data_offsets.empty() ? 0 : data_offsets[i]});
+  }
+  args.p = {p.get(), p_offset};
+  args.q = {q.get(), q_offset};
+  if (length == 0 && !data.empty()) {
+    if (unit == 0) unit = std::lcm<uint64_t>(data[0]->block_size(), 16);
+    length = parity_common_length(args.data, args.p, args.q, unit);
+  }
+  args.length = length;
+  return args;
+}
+
+// kIoInvalid becomes ValueError, any other failure RuntimeError; the
+// text names the rule that was broken.
+void parity_raise(const char* what, int status, const ParityReport& report) {
+  if (status == kIoOk) return;
+  const std::string text = std::string(what) + ": " + report.error +
+                           " (status " + std::to_string(status) + ")";
+  if (status == kIoInvalid) throw std::invalid_argument(text);
+  throw std::runtime_error(text);
+}
+
+// Little-endian bytes: granule g is byte g//8, bit g%8.
+py::bytes bitmap_bytes(const std::vector<uint64_t>& words, uint64_t granules) {
+  std::string raw((granules + 7) / 8, '\0');
+  for (size_t i = 0; i < raw.size(); ++i) {
+    raw[i] = static_cast<char>((words[i / 8] >> (8 * (i % 8))) & 0xFF);
+  }
+  return py::bytes(raw);
+}
+
+py::dict parity_stats_dict(const DiffStats& stats,
+                           const std::vector<uint64_t>& words) {
+  py::dict d;
+  d["granules"] = stats.granules;
+  d["mismatched"] = stats.mismatched;
+  d["first_mismatches"] = stats.first_mismatches;
+  d["bitmap"] = bitmap_bytes(words, stats.granules);
+  return d;
 }
 
 }  // namespace
@@ -722,6 +786,105 @@ PYBIND11_MODULE(_hipstore, m) {
      "Compare every replica of a replicated bdev with child 0; with "
      "repair, overwrite mismatching granules from it (refused while the "
      "bdev is claimed)");
+
+  m.def("parity_encode", [](std::vector<BdevPtr> data, BdevPtr p, BdevPtr q,
+                            std::vector<uint64_t> data_offsets,
+                            uint64_t p_offset, uint64_t q_offset,
+                            uint64_t length) {
+    const ParityArgs a = parity_args(data, p, q, data_offsets, p_offset,
+                                     q_offset, length, 0);
+    ParityReport report;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_parity_encode_sync(a.data, a.p, a.q, a.length, &report);
+    }
+    parity_raise("parity_encode", status, report);
+    py::dict d;
+    d["length"] = a.length;
+    d["on_gpu"] = report.on_gpu;
+    return d;
+  }, py::arg("data"), py::arg("p") = py::none(), py::arg("q") = py::none(),
+     py::arg("data_offsets") = std::vector<uint64_t>{},
+     py::arg("p_offset") = 0, py::arg("q_offset") = 0, py::arg("length") = 0,
+     "Write P (XOR) and / or Q (Reed-Solomon over GF(2^8)) parity of up to "
+     "32 data bdevs (on-GPU for HBM sets). length=0: the whole of the "
+     "shortest member");
+
+  m.def("parity_check", [](std::vector<BdevPtr> data, BdevPtr p, BdevPtr q,
+                           uint32_t granule, uint32_t max_report,
+                           std::vector<uint64_t> data_offsets,
+                           uint64_t p_offset, uint64_t q_offset,
+                           uint64_t length) {
+    if (granule == 0 && !data.empty() && data[0]) {
+      granule = static_cast<uint32_t>(data[0]->block_size());
+    }
+    const ParityArgs a = parity_args(data, p, q, data_offsets, p_offset,
+                                     q_offset, length, granule);
+    ParityReport report;
+    ParityCheck check;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_parity_check_sync(a.data, a.p, a.q, a.length, granule,
+                                      max_report, &check, &report);
+    }
+    parity_raise("parity_check", status, report);
+    py::dict d;
+    d["granule"] = granule;
+    d["on_gpu"] = report.on_gpu;
+    d["p"] = parity_stats_dict(check.p, check.p_bitmap);
+    d["q"] = parity_stats_dict(check.q, check.q_bitmap);
+    return d;
+  }, py::arg("data"), py::arg("p") = py::none(), py::arg("q") = py::none(),
+     py::arg("granule") = 0, py::arg("max_report") = 16,
+     py::arg("data_offsets") = std::vector<uint64_t>{},
+     py::arg("p_offset") = 0, py::arg("q_offset") = 0, py::arg("length") = 0,
+     "Recompute P / Q of the data bdevs and compare with the stored parity, "
+     "granule by granule; \"p\" and \"q\" are shaped like bdev_diff results");
+
+  m.def("parity_rebuild", [](std::vector<BdevPtr> data, py::list lost,
+                             BdevPtr p, BdevPtr q,
+                             std::vector<uint64_t> data_offsets,
+                             uint64_t p_offset, uint64_t q_offset,
+                             uint64_t length) {
+    std::vector<int> lost_ids;
+    for (py::handle item : lost) {
+      if (py::isinstance<py::str>(item)) {
+        const std::string name = item.cast<std::string>();
+        if (name != "p" && name != "q") {
+          throw std::invalid_argument("parity_rebuild: lost entries are data "
+                                      "indices, \"p\" or \"q\"");
+        }
+        lost_ids.push_back(name == "p" ? kParityLostP : kParityLostQ);
+      } else {
+        const int64_t index = item.cast<int64_t>();
+        // Anything that is no index stays invalid for the core to name.
+        lost_ids.push_back(index < 0 || index > INT32_MAX
+                               ? INT32_MAX
+                               : static_cast<int>(index));
+      }
+    }
+    const ParityArgs a = parity_args(data, p, q, data_offsets, p_offset,
+                                     q_offset, length, 0);
+    ParityReport report;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_parity_rebuild_sync(a.data, a.p, a.q, a.length, lost_ids,
+                                        &report);
+    }
+    parity_raise("parity_rebuild", status, report);
+    py::dict d;
+    d["length"] = a.length;
+    d["on_gpu"] = report.on_gpu;
+    return d;
+  }, py::arg("data"), py::arg("lost"), py::arg("p") = py::none(),
+     py::arg("q") = py::none(),
+     py::arg("data_offsets") = std::vector<uint64_t>{},
+     py::arg("p_offset") = 0, py::arg("q_offset") = 0, py::arg("length") = 0,
+     "Rewrite the one or two members named by `lost` (data indices, \"p\", "
+     "\"q\") from the others; the bdevs in those slots are the targets");
 
   m.def("persistent_probe", &persistent_probe, py::arg("device") = 0,
         py::arg("flags") = 1,

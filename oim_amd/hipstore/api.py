@@ -7,7 +7,7 @@ docs/spec.md "hipstored JSON-RPC surface".
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Union
 
 from .client import Client
 
@@ -270,6 +270,66 @@ def bdev_replica_scrub(client: Client, name: str, repair: bool = False,
     if max_report is not None:
         params["max_report"] = max_report
     return client.invoke("bdev_replica_scrub", params)
+
+
+def _parity_params(data: List[str], p: Optional[str], q: Optional[str],
+                   offset: int, length: Optional[int]) -> Dict:
+    params: Dict = {"data": list(data)}
+    if p is not None:
+        params["p"] = p
+    if q is not None:
+        params["q"] = q
+    if offset:
+        params["offset"] = offset
+    if length is not None:
+        params["length"] = length
+    return params
+
+
+def bdev_parity_encode(client: Client, data: List[str],
+                       p: Optional[str] = None, q: Optional[str] = None,
+                       offset: int = 0, length: Optional[int] = None) -> Dict:
+    """Write P (XOR) and/or Q (Reed-Solomon over GF(2^8)) parity of up to
+    32 data bdevs to the bdevs `p` / `q` (on-GPU for HBM sets). The order
+    of `data` is the member index. Offline only: run it while the set is
+    quiescent.
+
+    Returns {length, on_gpu}. length defaults to the whole of the
+    shortest member."""
+    return client.invoke("bdev_parity_encode",
+                         _parity_params(data, p, q, offset, length))
+
+
+def bdev_parity_scrub(client: Client, data: List[str],
+                      p: Optional[str] = None, q: Optional[str] = None,
+                      offset: int = 0, length: Optional[int] = None,
+                      granule: Optional[int] = None,
+                      max_report: Optional[int] = None) -> Dict:
+    """Recompute the parity of `data` and compare it with what `p` / `q`
+    hold, granule by granule. Only reads.
+
+    Returns {granule, on_gpu, p: {granules, mismatched,
+    first_mismatches}, q: {...}} with an entry for each parity given."""
+    params = _parity_params(data, p, q, offset, length)
+    if granule is not None:
+        params["granule"] = granule
+    if max_report is not None:
+        params["max_report"] = max_report
+    return client.invoke("bdev_parity_scrub", params)
+
+
+def bdev_parity_rebuild(client: Client, data: List[str],
+                        lost: List[Union[int, str]],
+                        p: Optional[str] = None, q: Optional[str] = None,
+                        offset: int = 0, length: Optional[int] = None) -> Dict:
+    """Rewrite the one or two members named by `lost` (indices into
+    `data`, "p" or "q") from the others; the bdevs in those slots are the
+    targets. Offline only.
+
+    Returns {length, on_gpu}."""
+    params = _parity_params(data, p, q, offset, length)
+    params["lost"] = list(lost)
+    return client.invoke("bdev_parity_rebuild", params)
 
 
 def bdev_export_delta(client: Client, name: str, path: str,
