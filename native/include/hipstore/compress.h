@@ -1,0 +1,120 @@
+// Compressed checkpoints: the HSLZ1 granule codec and the marked
+// compress / decompress calls under version-2 delta files (delta.h).
+//
+// HSLZ1. A granule of G bytes (512 <= G <= 16384, G % 16 == 0) is
+// compressed on its own and stored either as a legal LZ4 block (token,
+// literal-length extension bytes, literals, 2-byte little-endian offset,
+// match-length extension bytes; minimum match 4; the last 5 bytes are
+// literals; no match starts after G - 12) or, when that block would not
+// be smaller than G, as the G raw bytes. A stored size of G means raw.
+// Any LZ4 block decoder decodes a stored block.
+//
+// The parse is normative: the host compressor below and
+// k_lz_compress_marked (compress_ops.hip) emit identical bytes, so a
+// file is fully determined by the content whichever path wrote it.
+//   - table: 2048 slots, each empty or a position; hash(v) =
+//     (v * 2654435761 mod 2^32) >> 21 of the little-endian u32 v.
+//   - anchor = p = 0. While p <= G - 12, take the window of positions
+//     q = p + l, 0 <= l < 64, q <= G - 12.
+//   - Every q reads its candidate c = table[hash(u32 at q)] before any
+//     position of the window is inserted. c is valid iff the slot is not
+//     empty and the u32 at c equals the u32 at q (c < q and q - c <=
+//     65535 hold by construction).
+//   - The winner is the lowest q with a valid candidate. The positions
+//     of the window up to and including the winner (all of them without
+//     a winner) are inserted; a slot takes the greatest position
+//     inserted into it, so the table never depends on an order.
+//   - No winner: p += 64. Otherwise the match (q, c) of length 4 is
+//     extended byte by byte while q + length < G - 5 and the bytes are
+//     equal; the sequence (literals [anchor, q), offset q - c, length) is
+//     emitted; anchor = p = q + length.
+//   - The bytes from anchor to G are emitted as the final literals.
+
+#pragma once
+
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "hipstore/bdev.h"
+
+namespace hipstore {
+
+constexpr uint32_t kLzMinGranule = 512;
+constexpr uint32_t kLzMaxGranule = 16384;
+constexpr uint32_t kLzHashBits = 11;
+constexpr uint32_t kLzHashMul = 2654435761u;
+constexpr uint32_t kLzWindow = 64;
+
+inline bool lz_granule_ok(uint64_t granule) {
+  return granule >= kLzMinGranule && granule <= kLzMaxGranule &&
+         granule % 16 == 0;
+}
+
+// A stored piece of `size` bytes starts 16-byte aligned in a window's
+// dense stream and takes this much of it.
+inline uint64_t lz_padded(uint64_t size) { return (size + 15) & ~15ull; }
+
+// Compresses in[0, granule) into out[0, granule) and returns the stored
+// size, 1 .. granule (granule = raw copy). lz_granule_ok required.
+uint32_t lz_compress_granule(const uint8_t* in, uint32_t granule, uint8_t* out);
+
+// Token walk without copying: true iff `piece` of `size` bytes is the raw
+// granule (size == granule) or a block whose every offset is >= 1 and <=
+// the bytes produced so far, whose reads stay inside the piece, whose
+// output ends at exactly `granule` and which keeps the end-of-block
+// rules (last sequence literals only, at least 5 of them unless the
+// block is one literal run; no match starts after granule - 12). `why`
+// receives the broken rule.
+bool lz_validate_granule(const uint8_t* piece, uint64_t size, uint32_t granule,
+                         std::string* why = nullptr);
+
+// Decodes a stored piece into out[0, granule); false (with `why`) for
+// exactly the pieces lz_validate_granule refuses. Never reads outside
+// the piece or writes outside out.
+bool lz_decompress_granule(const uint8_t* piece, uint64_t size,
+                           uint32_t granule, uint8_t* out,
+                           std::string* why = nullptr);
+
+// bdev_pack_marked_sync with every granule compressed: sink(data, sizes,
+// first_rank, count) receives the stored sizes of marked granules
+// first_rank .. first_rank + count - 1 and their pieces in `data`, piece
+// i at the sum of lz_padded(sizes[j]) over j < i, pad bytes 0. Same
+// chunks, validation and path selection as bdev_pack_marked_sync; also
+// kIoInvalid unless lz_granule_ok. An HBM bdev with a usable GPU runs
+// k_lz_compress_marked and k_gather_var per window, so only stored bytes
+// cross PCIe; every other bdev goes through bdev_pack_marked_sync's
+// generic path and lz_compress_granule. Both paths hand the sink the
+// same chunks and the same bytes.
+using CompressSink = std::function<int(const uint8_t* data,
+                                       const uint32_t* sizes,
+                                       uint64_t first_rank, uint64_t count)>;
+int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
+                              uint32_t granule,
+                              const std::vector<uint64_t>& bitmap,
+                              uint64_t staging_bytes, const CompressSink& sink,
+                              uint64_t* packed = nullptr,
+                              std::string* error = nullptr);
+
+// The inverse: source(data, sizes, first_rank, count) fills the stored
+// sizes and the pieces of the next chunk in the layout above (`data` has
+// room for count * granule bytes). Every piece is checked with
+// lz_validate_granule on the host before anything is decoded or reaches
+// the GPU; a bad piece is kIoInvalid and `error` names the granule.
+// Chunks delivered before it stay written. HBM bdevs decode in
+// k_lz_decompress_marked, which bounds every index on its own and
+// reports a piece it had to give up in a per-window flag array: such a
+// piece is kIoFailed.
+using DecompressSource = std::function<int(uint8_t* data, uint32_t* sizes,
+                                           uint64_t first_rank,
+                                           uint64_t count)>;
+int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
+                                uint64_t length, uint32_t granule,
+                                const std::vector<uint64_t>& bitmap,
+                                uint64_t staging_bytes,
+                                const DecompressSource& source,
+                                uint64_t* unpacked = nullptr,
+                                std::string* error = nullptr);
+
+}  // namespace hipstore

@@ -16,6 +16,22 @@
 //     granules: u32 count, u32 crc32c(payload), count * granule bytes
 //   trailer, 16 bytes: "HSDEND1\0", u64 n_marked
 // All CRCs are crc32c_sw(0, ...).
+//
+// "hipstore delta file, version 2" holds the same granules compressed
+// (HSLZ1, compress.h) and is what an export with `compress` writes;
+// without it every file is version 1, byte for byte as above. Version 2
+// differs in three places:
+//   - version = 2 and flags bit 1 (kDeltaFlagLz) set; one implies the other
+//   - the two spare header words are one u64 record_area_bytes, the
+//     length of the record stream, so the exact file length still follows
+//     from the header
+//   - records, cut as in version 1: u32 count, u32 crc32c(payload),
+//     u32 payload_bytes, u32 0, then the payload: count u32 stored sizes
+//     (1 .. granule; granule = raw), then the pieces back to back,
+//     unpadded
+// Import tells the versions apart by itself. A version-2 record's CRC,
+// its sizes and then every piece (lz_validate_granule) are checked
+// before a byte of it is decoded or reaches the GPU.
 
 #pragma once
 
@@ -28,7 +44,9 @@
 namespace hipstore {
 
 constexpr uint32_t kDeltaVersion = 1;
+constexpr uint32_t kDeltaVersionLz = 2;
 constexpr uint32_t kDeltaFlagFull = 1;
+constexpr uint32_t kDeltaFlagLz = 2;
 constexpr uint64_t kDeltaHeaderBytes = 64;
 constexpr uint64_t kDeltaTrailerBytes = 16;
 constexpr uint64_t kDeltaRecordBytes = 1ull << 20;
@@ -42,6 +60,10 @@ struct DeltaInfo {
   uint64_t n_granules = 0;
   uint64_t n_marked = 0;  // granules in the file (saved / applied)
   uint64_t file_bytes = 0;
+  bool compressed = false;  // version 2
+  // Bytes the granules take in the file: n_marked * granule, or the sum
+  // of the stored sizes of a compressed file.
+  uint64_t stored_bytes = 0;
 };
 
 // Every call returns an IoStatus and, on failure, a one-line reason in
@@ -138,9 +160,9 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
 // the base state and replaces `base` (giving both is kIoInvalid): one
 // fingerprint pass of `src`, then granule g is exported when it lies at
 // or past the map's n_granules (a grown volume) or its fingerprint
-// differs. The file is a normal version-1 delta (flags 0), byte for byte
-// what a clone of that state as `base` gives, up to the fingerprint's
-// 2^-64 miss probability. granule 0 = the map's granule; any other
+// differs. The file is a normal delta (flags 0), byte for byte what a
+// clone of that state as `base` gives, up to the fingerprint's 2^-64
+// miss probability. granule 0 = the map's granule; any other
 // granule than the map's, another block size or a map larger than `src`
 // is kIoInvalid.
 //
@@ -151,6 +173,10 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
 // that lands between the fingerprint pass and the pack pass of a claimed
 // volume leaves the new map older than the exported data, so the next
 // delta exports that granule again: the safe direction.
+//
+// `compress` writes a version-2 file; the granule must then satisfy
+// lz_granule_ok (kIoInvalid otherwise). Maps are unaffected: they
+// describe the volume, not the file.
 struct DeltaMaps {
   std::string base_map;
   std::string map_out;
@@ -158,6 +184,7 @@ struct DeltaMaps {
 };
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
-                      DeltaInfo* stats, std::string* error);
+                      DeltaInfo* stats, std::string* error,
+                      bool compress = false);
 
 }  // namespace hipstore

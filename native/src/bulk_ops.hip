@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "gpu_internal.h"
+#include "marked_internal.h"
 #include "hipstore/crc32c.h"
 #include "hipstore/engine.h"
 #include "hipstore/fingerprint.h"
@@ -178,13 +179,6 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_copy_marked(
 // never visited, and they lie above every valid bit, so they are never
 // counted either. `window_count` bounds the slot: nothing outside
 // [0, window_count * granule) of the dense buffer is touched.
-struct MarkedWindow {
-  uint64_t g_begin;
-  uint64_t g_end;
-  uint32_t first_rank;  // marked granules before g_begin
-  uint32_t count;       // marked granules in the window
-};
-
 template <bool kPack>
 __device__ __forceinline__ void marked_window_walk(
     uint8_t* __restrict__ bdev_base, uint8_t* __restrict__ dense,
@@ -481,14 +475,11 @@ int hbm_copy_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
 // Granule compare / marked copy
 // ---------------------------------------------------------------------------
 
-namespace {
-
-// Shared validation; one bdev is the pair (bdev, bdev). Bounds are
-// phrased by subtraction so no 64-bit sum can wrap. A call that takes a
-// bitmap passes it: it must cover the range.
+// Shared validation (marked_internal.h). Bounds are phrased by
+// subtraction so no 64-bit sum can wrap.
 bool granule_ranges_ok(Bdev* a, uint64_t a_offset, Bdev* b, uint64_t b_offset,
                        uint64_t length, uint32_t granule,
-                       const std::vector<uint64_t>* bitmap = nullptr) {
+                       const std::vector<uint64_t>* bitmap) {
   if (a == nullptr || b == nullptr) return false;
   const uint64_t bs = a->block_size();
   if (bs == 0 || bs != b->block_size() || bs > kDiffHostChunk) return false;
@@ -531,6 +522,8 @@ uint32_t granule_grid(uint64_t n_granules) {
   return static_cast<uint32_t>(
       std::min<uint64_t>((n_granules + 63) / 64, 2048));
 }
+
+namespace {
 
 // Largest multiple of the block size that fits the generic-path cap.
 uint64_t host_chunk_bytes(Bdev* bdev) {
@@ -577,21 +570,9 @@ int copy_span_generic(Bdev* src, uint64_t src_offset, Bdev* dst,
   return kIoOk;
 }
 
-// What every call that takes a bitmap works from: the pinned copy of
-// the caller's bitmap with stray tail bits cleared (the kernels read it
-// in place), the number of marks, and, when asked for, the exclusive
-// prefix popcount that k_pack_marked / k_unpack_marked read.
-// `chunk_granules` belongs to pack / unpack, which set it.
-struct MarkedPlan {
-  uint64_t n_granules = 0;
-  uint64_t n_words = 0;
-  uint64_t marked = 0;
-  uint64_t chunk_granules = 0;
-  unsigned long long* words = nullptr;
-  uint32_t* ranks = nullptr;
-};
+}  // namespace
 
-// `bitmap` holds at least ceil(n_granules / 64) words (granule_ranges_ok).
+// MarkedPlan (marked_internal.h) in this thread's pinned buffers.
 MarkedPlan build_marked_plan(uint64_t n_granules,
                              const std::vector<uint64_t>& bitmap,
                              bool want_ranks) {
@@ -613,6 +594,8 @@ MarkedPlan build_marked_plan(uint64_t n_granules,
   plan.marked = rank;
   return plan;
 }
+
+namespace {
 
 // Walks a plan's runs of consecutive marked granules in ascending
 // order. next() hands out the run at or after the cursor, cut to
@@ -761,13 +744,6 @@ int bdev_copy_marked_sync(Bdev* src, uint64_t src_offset, Bdev* dst,
 // Marked gather / scatter through a dense staging stream
 // ---------------------------------------------------------------------------
 
-namespace {
-
-constexpr uint64_t kDefaultStagingHalf = 16ull << 20;
-
-// The window that starts at granule `g_begin` and holds the next
-// min(chunk, marks left) marked granules: it ends right after the last
-// of them.
 MarkedWindow next_marked_window(const MarkedPlan& plan, uint64_t g_begin,
                                 uint64_t first_rank) {
   MarkedWindow win;
@@ -808,28 +784,7 @@ void wait_marked_event(hipEvent_t event) {
   HIP_CHECK(err);
 }
 
-// A one-shot stream with one event per half of a two-half pinned
-// buffer: the window loops below launch into one half while the host
-// works on the other.
-struct HalvesStream : ScopedStream {
-  hipEvent_t done[2] = {nullptr, nullptr};
-
-  explicit HalvesStream(int device) : ScopedStream(device) {
-    for (hipEvent_t& e : done) {
-      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-  }
-  ~HalvesStream() {
-    (void)hipStreamSynchronize(stream);  // before the events go
-    for (hipEvent_t e : done) {
-      if (e != nullptr) (void)hipEventDestroy(e);
-    }
-  }
-};
-
-uint32_t marked_window_grid(const MarkedWindow& win) {
-  return granule_grid((win.g_end + 63) / 64 * 64 - win.g_begin / 64 * 64);
-}
+namespace {
 
 // What both GPU window loops run on. One stream and one event per
 // staging half: launch window k+1, then wait for window k only. The

@@ -49,7 +49,7 @@ uint64_t record_stream_bytes(uint64_t total, uint64_t unit,
 }
 
 int InFile::open(const std::string& path, const Format& format,
-                 std::string* error) {
+                 std::string* error, const Format* newer) {
   format_ = &format;
   in_.fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
   if (in_.fd < 0) return fail(error, kIoFailed, errno_text("open " + path));
@@ -72,7 +72,9 @@ int InFile::open(const std::string& path, const Format& format,
   if (get_u32(h + 60) != crc32c_sw(0, h, 60)) {
     return fail(error, kIoInvalid, "header CRC mismatch");
   }
-  if (get_u32(h + 8) != format.version) {
+  if (newer != nullptr && get_u32(h + 8) == newer->version) {
+    format_ = newer;
+  } else if (get_u32(h + 8) != format.version) {
     return fail(error, kIoInvalid, "unsupported " + noun + " version");
   }
   header.block_size = get_u32(h + 12);
@@ -165,6 +167,77 @@ int RecordReader::next_record(std::string* error) {
   return kIoOk;
 }
 
+VarRecordReader::VarRecordReader(const InFile* in, uint64_t offset,
+                                 uint64_t area, uint64_t max_unit,
+                                 uint64_t per_record, uint64_t total)
+    : in_(in), offset_(offset), area_(area), max_unit_(max_unit),
+      per_record_(per_record), left_(total),
+      buf_(buffer_units(per_record, total) * (4 + max_unit)) {}
+
+int VarRecordReader::next(const uint8_t** unit, uint32_t* size,
+                          std::string* error) {
+  if (pos_ == have_) {
+    const int status = next_record(error);
+    if (status != kIoOk) return status;
+  }
+  *size = get_u32(&buf_[pos_ * 4]);
+  *unit = &buf_[at_];
+  at_ += *size;
+  ++pos_;
+  return kIoOk;
+}
+
+int VarRecordReader::next_record(std::string* error) {
+  const uint64_t want = std::min(per_record_, left_);
+  if (want == 0) return fail(error, kIoInvalid, "record stream exhausted");
+  const std::string name = "record " + std::to_string(index_);
+  uint8_t head[kVarRecordHead];
+  if (area_ < kVarRecordHead) {
+    return fail(error, kIoInvalid, name + " lies past the record area");
+  }
+  if (!in_->read(head, sizeof(head), offset_)) {
+    return fail(error, kIoFailed, "cannot read record header");
+  }
+  const uint64_t payload = get_u32(head + 8);
+  if (get_u32(head) != want || get_u32(head + 12) != 0) {
+    return fail(error, kIoInvalid, name + " has a wrong count");
+  }
+  // Between one byte and max_unit per unit, inside the area, and the
+  // last record ends the area.
+  if (payload < want * 5 || payload > want * (4 + max_unit_) ||
+      payload > area_ - kVarRecordHead ||
+      (left_ == want && payload != area_ - kVarRecordHead)) {
+    return fail(error, kIoInvalid, name + " has a wrong payload length");
+  }
+  if (!in_->read(buf_.data(), payload, offset_ + kVarRecordHead)) {
+    return fail(error, kIoFailed, "cannot read record payload");
+  }
+  if (crc32c_sw(0, buf_.data(), payload) != get_u32(head + 4)) {
+    return fail(error, kIoInvalid, name + " CRC mismatch");
+  }
+  uint64_t sum = want * 4;
+  for (uint64_t i = 0; i < want; ++i) {
+    const uint64_t size = get_u32(&buf_[i * 4]);
+    if (size == 0 || size > max_unit_) {
+      return fail(error, kIoInvalid,
+                  name + ": stored size " + std::to_string(size) +
+                      " of its unit " + std::to_string(i) + " is out of range");
+    }
+    sum += size;
+  }
+  if (sum != payload) {
+    return fail(error, kIoInvalid, name + ": sizes disagree with the payload");
+  }
+  offset_ += kVarRecordHead + payload;
+  area_ -= kVarRecordHead + payload;
+  left_ -= want;
+  have_ = want;
+  pos_ = 0;
+  at_ = want * 4;
+  ++index_;
+  return kIoOk;
+}
+
 OutFile::OutFile(const std::string& final_path)
     : final_(final_path), tmp_(final_path + ".tmp") {}
 
@@ -172,13 +245,9 @@ OutFile::~OutFile() {
   if (out_.fd >= 0 && !published_) unlink(tmp_.c_str());
 }
 
-int OutFile::begin(const Format& format, const Header& header,
-                   std::string* error) {
-  format_ = &format;
-  out_.fd = ::open(tmp_.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC,
-                   0644);
-  if (out_.fd < 0) return fail(error, kIoFailed, errno_text("open " + tmp_));
-  uint8_t raw[kHeaderBytes];
+namespace {
+
+void encode_header(const Format& format, const Header& header, uint8_t* raw) {
   memcpy(raw, format.magic, 8);
   put_u32(raw + 8, format.version);
   put_u32(raw + 12, header.block_size);
@@ -188,10 +257,37 @@ int OutFile::begin(const Format& format, const Header& header,
   put_u64(raw + 32, header.n_granules);
   memcpy(raw + 40, header.owned, sizeof(header.owned));
   put_u32(raw + 60, crc32c_sw(0, raw, 60));
+}
+
+}  // namespace
+
+int OutFile::begin(const Format& format, const Header& header,
+                   std::string* error) {
+  format_ = &format;
+  out_.fd = ::open(tmp_.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC,
+                   0644);
+  if (out_.fd < 0) return fail(error, kIoFailed, errno_text("open " + tmp_));
+  uint8_t raw[kHeaderBytes];
+  encode_header(format, header, raw);
   if (!write(raw, sizeof(raw))) {
     return fail(error, kIoFailed, errno_text("write " + tmp_));
   }
   return kIoOk;
+}
+
+bool OutFile::rewrite_header(const Header& header) {
+  uint8_t raw[kHeaderBytes];
+  encode_header(*format_, header, raw);
+  for (size_t done = 0; done < sizeof(raw) && !failed_;) {
+    const ssize_t n = pwrite(out_.fd, raw + done, sizeof(raw) - done,
+                             static_cast<off_t>(done));
+    if (n >= 0) {
+      done += static_cast<size_t>(n);
+    } else if (errno != EINTR) {
+      failed_ = true;
+    }
+  }
+  return !failed_;
 }
 
 bool OutFile::write(const void* data, size_t len) {
@@ -248,6 +344,38 @@ int RecordWriter::add(const uint8_t* data, uint64_t count) {
       have_ = 0;
     }
   }
+  return kIoOk;
+}
+
+VarRecordWriter::VarRecordWriter(OutFile* out, uint64_t max_unit,
+                                 uint64_t per_record, uint64_t total)
+    : out_(out), max_unit_(max_unit), per_record_(per_record), left_(total) {}
+
+int VarRecordWriter::add(const uint8_t* unit, uint32_t size) {
+  const uint64_t want = std::min(per_record_, left_);
+  if (want == 0 || size == 0 || size > max_unit_) return kIoFailed;
+  uint8_t raw[4];
+  put_u32(raw, size);
+  sizes_.insert(sizes_.end(), raw, raw + 4);
+  units_.insert(units_.end(), unit, unit + size);
+  unit_bytes_ += size;
+  if (++have_ < want) return kIoOk;
+  uint8_t head[kVarRecordHead];
+  put_u32(head, static_cast<uint32_t>(have_));
+  put_u32(head + 4, crc32c_sw(crc32c_sw(0, sizes_.data(), sizes_.size()),
+                              units_.data(), units_.size()));
+  put_u32(head + 8, static_cast<uint32_t>(sizes_.size() + units_.size()));
+  put_u32(head + 12, 0);
+  if (!out_->write(head, sizeof(head)) ||
+      !out_->write(sizes_.data(), sizes_.size()) ||
+      !out_->write(units_.data(), units_.size())) {
+    return kIoFailed;
+  }
+  area_ += kVarRecordHead + sizes_.size() + units_.size();
+  left_ -= have_;
+  have_ = 0;
+  sizes_.clear();
+  units_.clear();
   return kIoOk;
 }
 

@@ -83,11 +83,23 @@ bool geometry_ok(uint64_t block_size, uint64_t granule, uint64_t volume_bytes,
 uint64_t record_stream_bytes(uint64_t total, uint64_t unit,
                              uint64_t per_record);
 
+// A stream of `total` units of variable length, 1 .. max_unit bytes
+// each, is cut into the same records: for each next min(remaining,
+// per_record) units, u32 count, u32 crc32c(payload), u32 payload_bytes,
+// u32 0, then the payload: count u32 sizes, then the units back to back.
+// Its length follows from the content, so the format keeps it in its
+// header.
+constexpr uint64_t kVarRecordHead = 16;
+
 class InFile {
  public:
   // Checks, in this order: regular file, room for header and trailer,
   // magic, header CRC, version. kIoFailed when the file cannot be opened.
-  int open(const std::string& path, const Format& format, std::string* error);
+  // `newer` is a later version of the same format (same magics) that is
+  // accepted too; format() tells which one the file is.
+  int open(const std::string& path, const Format& format, std::string* error,
+           const Format* newer = nullptr);
+  const Format& format() const { return *format_; }
   // The file is exactly header, `body` bytes and trailer.
   int check_length(uint64_t body, std::string* error) const;
   // End magic and count.
@@ -127,6 +139,31 @@ class RecordReader {
   std::vector<uint8_t> buf_;
 };
 
+// The reader of a variable-length record stream of `area` bytes at
+// `offset`: one unit per call, a record's CRC and its sizes (1 ..
+// max_unit, adding up to the payload) checked before any of its bytes
+// leave. The last unit must end the area exactly.
+class VarRecordReader {
+ public:
+  VarRecordReader(const InFile* in, uint64_t offset, uint64_t area,
+                  uint64_t max_unit, uint64_t per_record, uint64_t total);
+  // *unit points into the reader's buffer until the next call.
+  int next(const uint8_t** unit, uint32_t* size, std::string* error);
+  // Units not yet handed out.
+  uint64_t left() const { return left_ + (have_ - pos_); }
+
+ private:
+  int next_record(std::string* error);
+
+  const InFile* in_;
+  uint64_t offset_, area_, max_unit_, per_record_;
+  uint64_t left_;  // units in records not yet read
+  uint64_t have_ = 0, pos_ = 0;  // units in buf_, units of them handed out
+  uint64_t at_ = 0;  // of unit pos_ in buf_
+  uint64_t index_ = 0;
+  std::vector<uint8_t> buf_;
+};
+
 // Written as final_path + ".tmp"; the destructor removes a tmp file that
 // was not published.
 class OutFile {
@@ -137,6 +174,9 @@ class OutFile {
   int begin(const Format& format, const Header& header, std::string* error);
   // A failure stays: later writes fail too, and end() reports it.
   bool write(const void* data, size_t len);
+  // Replaces the header begin() wrote, for a field that is known only
+  // after the body. Same failure rule as write().
+  bool rewrite_header(const Header& header);
   // Writes the trailer and syncs: the tmp file is complete.
   int end(uint64_t count, std::string* error);
   int publish(std::string* error);
@@ -167,6 +207,29 @@ class RecordWriter {
   uint64_t left_;  // units not yet written
   uint64_t have_ = 0;  // units in buf_
   std::vector<uint8_t> buf_;
+};
+
+// Cuts `total` variable-length units into records, one unit per add().
+class VarRecordWriter {
+ public:
+  VarRecordWriter(OutFile* out, uint64_t max_unit, uint64_t per_record,
+                  uint64_t total);
+  // kIoFailed on a failed write, a size outside 1 .. max_unit or more
+  // units than announced.
+  int add(const uint8_t* unit, uint32_t size);
+  bool complete() const { return left_ == 0 && have_ == 0; }
+  // Bytes of the records written so far: the stream's area once complete.
+  uint64_t area() const { return area_; }
+  // Bytes of the units alone.
+  uint64_t unit_bytes() const { return unit_bytes_; }
+
+ private:
+  OutFile* out_;
+  uint64_t max_unit_, per_record_;
+  uint64_t left_;  // units not yet written
+  uint64_t have_ = 0;  // units in the open record
+  uint64_t area_ = 0, unit_bytes_ = 0;
+  std::vector<uint8_t> sizes_, units_;  // of the open record
 };
 
 }  // namespace checked_file

@@ -1,0 +1,769 @@
+// MI355X (gfx950) HSLZ1 compression of marked granules (definitions and
+// the normative parse in hipstore/compress.h): k_lz_compress_marked,
+// k_gather_var and k_lz_decompress_marked, their window loops and the
+// generic path. Like bulk_ops.hip, each call owns its stream, runs to
+// completion and returns.
+//
+// Work split: a wave takes one whole granule at a time and waves
+// grid-stride over the granules of the window's bitmap words (at most
+// 2048 workgroups), so the bit test and the whole parse are wave-uniform
+// and waves never wait for each other: there is no workgroup barrier in
+// this file. The slot of a granule comes from the bitmap and
+// rank_before_word exactly as in k_pack_marked.
+//
+// Data movement, compress: HBM -> LDS (16 B per lane) -> parse in LDS ->
+// block built in LDS -> HBM scratch slot `rank` (16 B per lane), stored
+// size -> pinned sizes[rank]. The host turns a window's sizes into
+// 16-byte-aligned offsets and k_gather_var moves only the stored bytes
+// over PCIe into the pinned dense buffer. Decompress is the way back:
+// pinned dense -> LDS piece -> LDS granule image -> HBM.
+//
+// LDS per wave: compress 2 * G + 8 KiB (granule, block, 2048 u32 table
+// slots), decompress 2 * G (piece, image). A workgroup has the 4, 2 or 1
+// waves that fit 64 KiB: compress 4 waves up to G = 4096 (64 KiB at
+// 4096), 2 up to 12288, 1 above; decompress 4 up to 8192, 2 above.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "gpu_internal.h"
+#include "hipstore/compress.h"
+#include "hipstore/engine.h"
+#include "marked_internal.h"
+
+namespace hipstore {
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// Kernels
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kLzTableBytes = (1u << kLzHashBits) * 4;
+constexpr uint32_t kLzMaxLds = 64u << 10;  // per workgroup
+
+// Orders this wave's LDS accesses: what one lane wrote before it, any
+// lane reads after it. LDS serves a wave's accesses in issue order, so
+// this only has to keep the compiler from moving them.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) {
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
+// fn(granule index, window slot) once per marked granule of the window,
+// by one wave. Unlike marked_window_walk (bulk_ops.hip), which gives a
+// workgroup a whole bitmap word, this walk gives every granule of the
+// window's words a wave of its own, grid-stride: a 16 MiB window of
+// 4 KiB granules is 64 words, and 64 workgroups leave most of the chip
+// idle under kernels that are bound by the latency of their serial
+// parse, not by bandwidth. The slot is the same pure function of the
+// bitmap and rank_before_word.
+template <typename Fn>
+__device__ __forceinline__ void lz_window_walk(
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, const MarkedWindow win,
+    Fn fn) {
+  const uint32_t n_waves = blockDim.x >> 6;
+  const uint64_t g_first = win.g_begin & ~63ull;
+  const uint64_t span = ((win.g_end + 63) & ~63ull) - g_first;
+  for (uint64_t v = static_cast<uint64_t>(blockIdx.x) * n_waves +
+                    uniform(threadIdx.x >> 6);
+       v < span; v += static_cast<uint64_t>(gridDim.x) * n_waves) {
+    const uint64_t g = g_first + v;  // wave-uniform, like all below
+    if (g < win.g_begin || g >= win.g_end) continue;
+    const unsigned long long word = bitmap[g >> 6];
+    const uint32_t bit = static_cast<uint32_t>(g & 63);
+    if (((word >> bit) & 1) == 0) continue;
+    const uint32_t slot =
+        uniform(rank_before_word[g >> 6]) - win.first_rank +
+        static_cast<uint32_t>(__popcll(word & ((1ull << bit) - 1)));
+    if (slot >= win.count) continue;  // bitmap and ranks disagree: stay inside
+    fn(g, slot);
+  }
+}
+
+// Little-endian u32 at byte `q` of an LDS image, q + 8 <= its size:
+// two aligned words and a funnel shift.
+__device__ __forceinline__ uint32_t lds_u32(const uint32_t* img, uint32_t q) {
+  const uint64_t pair =
+      static_cast<uint64_t>(img[(q >> 2) + 1]) << 32 | img[q >> 2];
+  return static_cast<uint32_t>(pair >> ((q & 3) * 8));
+}
+
+__device__ __forceinline__ uint32_t lz_ext_bytes(uint32_t len) {
+  return len >= 15 ? 1 + (len - 15) / 255 : 0;
+}
+
+// The extension bytes of `len` at out[o]: the 255s by all lanes, the
+// last byte by lane 0. Returns the position after them.
+__device__ __forceinline__ uint32_t lz_put_ext(uint8_t* out, uint32_t o,
+                                               uint32_t len, uint32_t lane) {
+  if (len < 15) return o;
+  const uint32_t n = (len - 15) / 255;
+  for (uint32_t i = lane; i < n; i += 64) out[o + i] = 255;
+  if (lane == 0) out[o + n] = static_cast<uint8_t>(len - 15 - n * 255);
+  return o + n + 1;
+}
+
+// One sequence at out[op]: token and lengths by lane 0, literals
+// in[anchor, anchor + lit) by all lanes, then the match unless len == 0.
+// false, with nothing written, when the block would not stay below G.
+__device__ __forceinline__ bool lz_emit(const uint8_t* in, uint8_t* out,
+                                        uint32_t& op, uint32_t anchor,
+                                        uint32_t lit, uint32_t offset,
+                                        uint32_t len, uint32_t granule,
+                                        uint32_t lane) {
+  const uint32_t ml = len != 0 ? len - 4 : 0;
+  const uint32_t need =
+      1 + lz_ext_bytes(lit) + lit + (len != 0 ? 2 + lz_ext_bytes(ml) : 0);
+  if (op + need >= granule) return false;
+  uint32_t o = op;
+  if (lane == 0) {
+    out[o] = static_cast<uint8_t>(min(lit, 15u) << 4 | min(ml, 15u));
+  }
+  o = lz_put_ext(out, o + 1, lit, lane);
+  for (uint32_t i = lane; i < lit; i += 64) out[o + i] = in[anchor + i];
+  o += lit;
+  if (len != 0) {
+    if (lane == 0) {
+      out[o] = static_cast<uint8_t>(offset);
+      out[o + 1] = static_cast<uint8_t>(offset >> 8);
+    }
+    o = lz_put_ext(out, o + 2, ml, lane);
+  }
+  op = o;
+  return true;
+}
+
+// The parse of compress.h over the LDS image `in`; the block goes to
+// `out`. Returns the stored size, `granule` for raw. Everything but the
+// per-lane candidate test is wave-uniform.
+__device__ __forceinline__ uint32_t lz_parse(const uint8_t* in, uint8_t* out,
+                                             uint32_t* table, uint32_t granule,
+                                             uint32_t lane) {
+  const uint32_t* in32 = reinterpret_cast<const uint32_t*>(in);
+  const uint32_t last = granule - 12;
+  uint32_t anchor = 0;
+  uint32_t op = 0;
+  uint32_t p = 0;
+  while (p <= last) {
+    const uint32_t q = p + lane;
+    const bool live = q <= last;
+    uint32_t hash = 0;
+    uint32_t cand = 0;
+    bool hit = false;
+    if (live) {
+      const uint32_t v = lds_u32(in32, q);
+      hash = (v * kLzHashMul) >> (32 - kLzHashBits);
+      const uint32_t slot = table[hash];  // position + 1, 0 = empty
+      if (slot != 0) {
+        cand = slot - 1;
+        hit = lds_u32(in32, cand) == v;
+      }
+    }
+    const unsigned long long hits = __ballot(hit);
+    const uint32_t winner =
+        hits != 0 ? static_cast<uint32_t>(__builtin_ctzll(hits)) : 64;
+    wave_sync();  // every candidate was read before any insert
+    if (live && lane <= winner) atomicMax(&table[hash], q + 1);
+    wave_sync();
+    if (hits == 0) {
+      p += kLzWindow;
+      continue;
+    }
+    const uint32_t wq = p + winner;
+    const uint32_t wc = static_cast<uint32_t>(
+        __shfl(static_cast<int>(cand), static_cast<int>(winner)));
+    // 64 bytes per step; the first lane that must stop ends the match.
+    const uint32_t cap = granule - 5 - wq;  // >= 7: wq <= granule - 12
+    uint32_t len = 4;
+    for (;;) {
+      const uint32_t i = len + lane;
+      const bool stop = i >= cap || in[wc + i] != in[wq + i];
+      const unsigned long long stops = __ballot(stop);
+      if (stops != 0) {
+        len += static_cast<uint32_t>(__builtin_ctzll(stops));
+        break;
+      }
+      len += 64;
+    }
+    if (!lz_emit(in, out, op, anchor, wq - anchor, wq - wc, len, granule,
+                 lane)) {
+      return granule;
+    }
+    anchor = p = wq + len;
+  }
+  if (!lz_emit(in, out, op, anchor, granule - anchor, 0, 0, granule, lane)) {
+    return granule;
+  }
+  return op;
+}
+
+// Scratch slot `slot` (stride G) receives the piece, its pad up to the
+// next multiple of 16 zeroed, and sizes[slot] its stored size: plain
+// loads and stores, no global atomics, nothing read that an earlier
+// launch left in scratch or sizes.
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_compress_marked(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ scratch,
+    uint32_t* __restrict__ sizes, const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule) {
+  extern __shared__ uint4 lz_lds[];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule >> 4;
+  uint8_t* in = reinterpret_cast<uint8_t*>(lz_lds) +
+                (threadIdx.x >> 6) * (2 * granule + kLzTableBytes);
+  uint8_t* out = in + granule;
+  uint32_t* table = reinterpret_cast<uint32_t*>(out + granule);
+  lz_window_walk(bitmap, rank_before_word, win, [&](uint64_t g, uint32_t slot) {
+    const uint4* __restrict__ pg =
+        reinterpret_cast<const uint4*>(src + g * granule);
+    uint4* in16 = reinterpret_cast<uint4*>(in);
+    uint4* table16 = reinterpret_cast<uint4*>(table);
+#pragma unroll 4
+    for (uint32_t i = lane; i < n16; i += 64) in16[i] = pg[i];
+    for (uint32_t i = lane; i < kLzTableBytes / 16; i += 64) {
+      table16[i] = make_uint4(0, 0, 0, 0);
+    }
+    wave_sync();
+    const uint32_t size = lz_parse(in, out, table, granule, lane);
+    // size < granule and granule % 16 == 0: the pad stays inside `out`.
+    if (size != granule && lane < ((16 - (size & 15)) & 15)) {
+      out[size + lane] = 0;
+    }
+    wave_sync();
+    const uint4* from =
+        size == granule ? in16 : reinterpret_cast<const uint4*>(out);
+    uint4* __restrict__ ps = reinterpret_cast<uint4*>(
+        scratch + static_cast<uint64_t>(slot) * granule);
+    for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) ps[i] = from[i];
+    if (lane == 0) sizes[slot] = size;
+    wave_sync();  // the next granule overwrites this LDS
+  });
+}
+
+// Piece r of a window, padded to 16 bytes, from scratch slot r to
+// dense + offsets[r]: wave per piece, 16 bytes per lane. The pad bytes
+// are the zeros k_lz_compress_marked left behind the piece. A size above
+// G cannot come from that kernel and is cut to G, so no access leaves
+// the slot.
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_gather_var(
+    const uint8_t* __restrict__ scratch, uint8_t* __restrict__ dense,
+    const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
+    uint32_t count, uint32_t granule) {
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t r = blockIdx.x * kWavesPerWg + (threadIdx.x >> 6); r < count;
+       r += gridDim.x * kWavesPerWg) {
+    const uint32_t size = min(uniform(sizes[r]), granule);
+    const uint4* __restrict__ ps = reinterpret_cast<const uint4*>(
+        scratch + static_cast<uint64_t>(r) * granule);
+    uint4* __restrict__ pd = reinterpret_cast<uint4*>(dense + offsets[r]);
+    for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) pd[i] = ps[i];
+  }
+}
+
+// One byte of the piece, the same for every lane.
+__device__ __forceinline__ uint32_t lz_byte(const uint8_t* piece, uint32_t ip) {
+  return uniform(piece[ip]);
+}
+
+// The rest of a length whose nibble was 15. false when the piece ends
+// inside it.
+__device__ __forceinline__ bool lz_take_ext(const uint8_t* piece,
+                                            uint32_t size, uint32_t& ip,
+                                            uint32_t& len) {
+  for (;;) {
+    if (ip >= size) return false;
+    const uint32_t b = lz_byte(piece, ip++);
+    len += b;  // at most 255 * size
+    if (b != 255) return true;
+  }
+}
+
+// Decodes piece[0, size), size < G, into image[0, G). Every read of the
+// piece is checked against `size` and every write of the image against
+// G before it happens; a sequence that would leave either ends the
+// decode with false. A match reads image[op - offset + (i mod offset)],
+// which lies below op for every i: correct down to offset 1 without any
+// order among the lanes.
+__device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
+                                          uint8_t* image, uint32_t granule,
+                                          uint32_t lane) {
+  uint32_t ip = 0;
+  uint32_t op = 0;
+  for (;;) {
+    if (ip >= size) return false;
+    const uint32_t token = lz_byte(piece, ip++);
+    uint32_t lit = token >> 4;
+    if (lit == 15 && !lz_take_ext(piece, size, ip, lit)) return false;
+    if (lit > size - ip || lit > granule - op) return false;
+    for (uint32_t i = lane; i < lit; i += 64) image[op + i] = piece[ip + i];
+    ip += lit;
+    op += lit;
+    if (ip == size) return op == granule;
+    if (size - ip < 2) return false;
+    const uint32_t offset = lz_byte(piece, ip) | lz_byte(piece, ip + 1) << 8;
+    ip += 2;
+    if (offset == 0 || offset > op) return false;
+    uint32_t len = token & 15;
+    if (len == 15 && !lz_take_ext(piece, size, ip, len)) return false;
+    len += 4;
+    if (len > granule - op) return false;
+    wave_sync();  // the literals above may be the match's source
+    const uint32_t from = op - offset;
+    const uint32_t step = 64 % offset;
+    uint32_t r = lane % offset;
+    for (uint32_t i = lane; i < len; i += 64) {
+      image[op + i] = image[from + r];
+      r += step;
+      if (r >= offset) r -= offset;
+    }
+    wave_sync();
+    op += len;
+  }
+}
+
+// Window slot `slot` of the dense buffer (sizes[slot] bytes at
+// offsets[slot]) becomes the marked granule of that rank; unmarked
+// granules are never written. bad[slot] is written for every piece of
+// the window: 0, or 1 when the piece could not be decoded, in which case
+// its granule is left alone.
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
+    uint8_t* __restrict__ dst, const uint8_t* __restrict__ dense,
+    const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
+    uint8_t* __restrict__ bad, const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule) {
+  extern __shared__ uint4 lz_lds[];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule >> 4;
+  uint4* piece16 = lz_lds + (threadIdx.x >> 6) * (2 * n16);
+  uint4* image16 = piece16 + n16;
+  lz_window_walk(bitmap, rank_before_word, win, [&](uint64_t g, uint32_t slot) {
+    const uint32_t size = uniform(sizes[slot]);
+    const uint4* __restrict__ pp =
+        reinterpret_cast<const uint4*>(dense + offsets[slot]);
+    uint4* __restrict__ pd = reinterpret_cast<uint4*>(dst + g * granule);
+    bool ok = size != 0 && size <= granule;
+    if (size == granule) {  // raw
+#pragma unroll 4
+      for (uint32_t i = lane; i < n16; i += 64) pd[i] = pp[i];
+    } else if (ok) {
+      for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) piece16[i] = pp[i];
+      wave_sync();
+      ok = lz_decode(reinterpret_cast<const uint8_t*>(piece16), size,
+                     reinterpret_cast<uint8_t*>(image16), granule, lane);
+      wave_sync();
+      if (ok) {
+#pragma unroll 4
+        for (uint32_t i = lane; i < n16; i += 64) pd[i] = image16[i];
+      }
+      wave_sync();  // the next piece overwrites this LDS
+    }
+    if (lane == 0) bad[slot] = ok ? 0 : 1;
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Window loops
+// ---------------------------------------------------------------------------
+
+// Waves per workgroup for `per_wave` bytes of LDS each.
+uint32_t lz_waves(uint32_t per_wave) {
+  return 4 * per_wave <= kLzMaxLds ? 4 : 2 * per_wave <= kLzMaxLds ? 2 : 1;
+}
+
+// Workgroups of `waves` waves for lz_window_walk: a wave per granule of
+// the window's bitmap words, at most 2048.
+uint32_t lz_window_grid(const MarkedWindow& win, uint32_t waves) {
+  const uint64_t span = (win.g_end + 63) / 64 * 64 - win.g_begin / 64 * 64;
+  return static_cast<uint32_t>(
+      std::min<uint64_t>((span + waves - 1) / waves, 2048));
+}
+
+// Device memory that grows on demand and keeps what it has, like
+// PinnedBuf; one device at a time.
+struct DeviceBuf {
+  uint8_t* ptr = nullptr;
+  uint64_t capacity = 0;
+  int device = -1;
+
+  DeviceBuf() = default;
+  ~DeviceBuf() { release(); }
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+
+  void release() {
+    if (ptr != nullptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    capacity = 0;
+  }
+  // The current device is `dev`.
+  uint8_t* reserve(int dev, uint64_t bytes) {
+    if (dev != device || bytes > capacity) {
+      release();
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ptr), bytes));
+      capacity = bytes;
+      device = dev;
+    }
+    return ptr;
+  }
+};
+
+// Per-thread buffers of the two calls, two halves each on the GPU path.
+struct CompressCtx {
+  DeviceBuf scratch;            // slots of stride G
+  PinnedBuf<uint8_t> dense;     // padded pieces
+  PinnedBuf<uint32_t> sizes;
+  PinnedBuf<uint64_t> offsets;  // of the pieces in `dense`
+  PinnedBuf<uint8_t> bad;       // k_lz_decompress_marked's flags
+};
+
+CompressCtx& compress_ctx() {
+  thread_local CompressCtx ctx;
+  return ctx;
+}
+
+// Exclusive offsets of a window's padded pieces.
+void piece_offsets(const uint32_t* sizes, uint64_t count, uint64_t* offsets) {
+  uint64_t at = 0;
+  for (uint64_t i = 0; i < count; ++i) {
+    offsets[i] = at;
+    at += lz_padded(sizes[i]);
+  }
+}
+
+// Granule index of marked granule number `rank` (error messages).
+uint64_t granule_of_rank(const std::vector<uint64_t>& bitmap, uint64_t rank) {
+  for (uint64_t w = 0; w < bitmap.size(); ++w) {
+    uint64_t word = bitmap[w];
+    const uint64_t have = static_cast<uint64_t>(__builtin_popcountll(word));
+    if (rank >= have) {
+      rank -= have;
+      continue;
+    }
+    for (; rank > 0; --rank) word &= word - 1;
+    return w * 64 + static_cast<uint64_t>(__builtin_ctzll(word));
+  }
+  return bitmap.size() * 64;
+}
+
+// Sizes, then every piece, of one window as a source delivered it;
+// fills `offsets`. kIoInvalid names the granule.
+int check_window(const std::vector<uint64_t>& bitmap, const uint8_t* data,
+                 const uint32_t* sizes, uint64_t first_rank, uint64_t count,
+                 uint32_t granule, uint64_t* offsets, std::string* error) {
+  uint64_t at = 0;
+  for (uint64_t i = 0; i < count; ++i) {
+    std::string why = "stored size out of range";
+    if (sizes[i] == 0 || sizes[i] > granule ||
+        !lz_validate_granule(data + at, sizes[i], granule, &why)) {
+      if (error != nullptr) {
+        *error = "granule " +
+                 std::to_string(granule_of_rank(bitmap, first_rank + i)) +
+                 ": bad compressed piece (" + why + ")";
+      }
+      return kIoInvalid;
+    }
+    offsets[i] = at;
+    at += lz_padded(sizes[i]);
+  }
+  return kIoOk;
+}
+
+// What both GPU window loops run on: HalvesStream's `done` events end a
+// half's last kernel, `packed` ends k_lz_compress_marked alone.
+struct LzStream : HalvesStream {
+  hipEvent_t packed[2] = {nullptr, nullptr};
+  uint32_t granule;
+  uint64_t chunk;  // granules per half
+  uint8_t* scratch = nullptr;
+  uint8_t* dense;
+  uint32_t* sizes;
+  uint64_t* offsets;
+  uint8_t* bad;
+  const unsigned long long* dev_words;
+  const uint32_t* dev_ranks;
+  uint8_t* base;  // the bdev's range in device memory
+
+  LzStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
+           const MarkedPlan& plan, bool compress)
+      : HalvesStream(device), granule(granule_bytes),
+        chunk(plan.chunk_granules),
+        dense(compress_ctx().dense.reserve(2 * chunk * granule)),
+        sizes(compress_ctx().sizes.reserve(2 * chunk)),
+        offsets(compress_ctx().offsets.reserve(2 * chunk)),
+        bad(compress_ctx().bad.reserve(2 * chunk)),
+        dev_words(device_view(plan.words)), dev_ranks(device_view(plan.ranks)),
+        base(static_cast<uint8_t*>(bdev->device_base()) + offset) {
+    if (compress) {
+      scratch = compress_ctx().scratch.reserve(device, 2 * chunk * granule);
+      for (hipEvent_t& e : packed) {
+        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      }
+    }
+  }
+  ~LzStream() {
+    (void)hipStreamSynchronize(stream);
+    for (hipEvent_t e : packed) {
+      if (e != nullptr) (void)hipEventDestroy(e);
+    }
+  }
+
+  void compress(const MarkedWindow& win, int half) {
+    const uint32_t per_wave = 2 * granule + kLzTableBytes;
+    const uint32_t waves = lz_waves(per_wave);
+    hipLaunchKernelGGL(k_lz_compress_marked, dim3(lz_window_grid(win, waves)),
+                       dim3(waves * 64), waves * per_wave, stream, base,
+                       scratch + half * chunk * granule,
+                       device_view(sizes + half * chunk), dev_words, dev_ranks,
+                       win, granule);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(packed[half], stream));
+  }
+
+  // After packed[half]: the sizes are in, the pieces follow.
+  void gather(const MarkedWindow& win, int half) {
+    piece_offsets(sizes + half * chunk, win.count, offsets + half * chunk);
+    const uint32_t grid = std::min<uint32_t>(
+        (win.count + kWavesPerWg - 1) / kWavesPerWg, 2048);
+    hipLaunchKernelGGL(k_gather_var, dim3(grid), dim3(kWavesPerWg * 64), 0,
+                       stream, scratch + half * chunk * granule,
+                       device_view(dense + half * chunk * granule),
+                       device_view(sizes + half * chunk),
+                       device_view(offsets + half * chunk), win.count, granule);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(done[half], stream));
+  }
+
+  void decompress(const MarkedWindow& win, int half) {
+    const uint32_t per_wave = 2 * granule;
+    const uint32_t waves = lz_waves(per_wave);
+    hipLaunchKernelGGL(k_lz_decompress_marked,
+                       dim3(lz_window_grid(win, waves)),
+                       dim3(waves * 64), waves * per_wave, stream, base,
+                       device_view(dense + half * chunk * granule),
+                       device_view(sizes + half * chunk),
+                       device_view(offsets + half * chunk),
+                       device_view(bad + half * chunk), dev_words, dev_ranks,
+                       win, granule);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(done[half], stream));
+  }
+};
+
+// Window k+1 is compressed while the sink has window k: one stream, so
+// the order on the device is compress k, gather k, compress k+1, ...
+int compress_gpu(LzStream& ls, const MarkedPlan& plan, const CompressSink& sink,
+                 uint64_t* packed) {
+  MarkedWindow cur = next_marked_window(plan, 0, 0);
+  ls.compress(cur, 0);
+  for (int half = 0;; half ^= 1) {
+    const uint64_t next_rank = cur.first_rank + static_cast<uint64_t>(cur.count);
+    wait_marked_event(ls.packed[half]);
+    ls.gather(cur, half);
+    MarkedWindow next{};
+    if (next_rank < plan.marked) {
+      next = next_marked_window(plan, cur.g_end, next_rank);
+      ls.compress(next, half ^ 1);
+    }
+    wait_marked_event(ls.done[half]);
+    const int status =
+        sink(ls.dense + half * ls.chunk * ls.granule,
+             ls.sizes + half * ls.chunk, cur.first_rank, cur.count);
+    if (status != 0) return status;
+    *packed = next_rank;
+    if (next_rank >= plan.marked) return kIoOk;
+    cur = next;
+  }
+}
+
+int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
+                   const std::vector<uint64_t>& bitmap,
+                   const DecompressSource& source, uint64_t* unpacked,
+                   std::string* error) {
+  uint32_t in_half[2] = {0, 0};  // pieces of the kernel that last used it
+  // After that kernel: did it give up on a piece?
+  auto gave_up = [&](int half) {
+    const uint8_t* bad = ls.bad + half * ls.chunk;
+    return std::any_of(bad, bad + in_half[half],
+                       [](uint8_t b) { return b != 0; });
+  };
+  uint64_t g_begin = 0;
+  uint64_t launched = 0;
+  int status = kIoOk;
+  for (int half = 0; launched < plan.marked && status == kIoOk; half ^= 1) {
+    const MarkedWindow win = next_marked_window(plan, g_begin, launched);
+    // The kernel two windows back read this half: let it finish first.
+    if (in_half[half] != 0) {
+      wait_marked_event(ls.done[half]);
+      if (gave_up(half)) status = kIoFailed;
+      in_half[half] = 0;
+      if (status != kIoOk) break;
+    }
+    uint8_t* data = ls.dense + half * ls.chunk * ls.granule;
+    uint32_t* sizes = ls.sizes + half * ls.chunk;
+    status = source(data, sizes, win.first_rank, win.count);
+    if (status == 0) {
+      status = check_window(bitmap, data, sizes, win.first_rank, win.count,
+                            ls.granule, ls.offsets + half * ls.chunk, error);
+    }
+    if (status != kIoOk) break;
+    ls.decompress(win, half);
+    in_half[half] = win.count;
+    launched += win.count;
+    g_begin = win.g_end;
+  }
+  HIP_CHECK(hipStreamSynchronize(ls.stream));
+  if (gave_up(0) || gave_up(1)) {
+    if (status == kIoOk) status = kIoFailed;
+    if (error != nullptr && error->empty()) {
+      *error = "k_lz_decompress_marked gave up on a piece";
+    }
+  }
+  *unpacked = launched;
+  return status;
+}
+
+// Generic paths: bdev_pack_marked_sync / bdev_unpack_marked_sync cut the
+// chunks, the host codec does the rest.
+int compress_generic(Bdev* src, uint64_t offset, uint64_t length,
+                     uint32_t granule, const std::vector<uint64_t>& bitmap,
+                     uint64_t staging_bytes, const CompressSink& sink,
+                     uint64_t* packed) {
+  std::vector<uint8_t> pieces;
+  std::vector<uint32_t> sizes;
+  return bdev_pack_marked_sync(
+      src, offset, length, granule, bitmap, staging_bytes,
+      [&](const uint8_t* data, uint64_t first_rank, uint64_t count) {
+        pieces.assign(count * granule, 0);  // pads are 0
+        sizes.resize(count);
+        uint64_t at = 0;
+        for (uint64_t i = 0; i < count; ++i) {
+          sizes[i] = lz_compress_granule(data + i * granule, granule,
+                                         pieces.data() + at);
+          at += lz_padded(sizes[i]);
+        }
+        return sink(pieces.data(), sizes.data(), first_rank, count);
+      },
+      packed);
+}
+
+int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
+                       uint32_t granule, const std::vector<uint64_t>& bitmap,
+                       uint64_t staging_bytes,
+                       const DecompressSource& source, uint64_t* unpacked,
+                       std::string* error) {
+  std::vector<uint8_t> pieces;
+  std::vector<uint32_t> sizes;
+  std::vector<uint64_t> offsets;
+  return bdev_unpack_marked_sync(
+      dst, offset, length, granule, bitmap, staging_bytes,
+      [&](uint8_t* data, uint64_t first_rank, uint64_t count) {
+        pieces.resize(count * granule);
+        sizes.resize(count);
+        offsets.resize(count);
+        int status = source(pieces.data(), sizes.data(), first_rank, count);
+        if (status == 0) {
+          status = check_window(bitmap, pieces.data(), sizes.data(), first_rank,
+                                count, granule, offsets.data(), error);
+        }
+        for (uint64_t i = 0; status == kIoOk && i < count; ++i) {
+          lz_decompress_granule(pieces.data() + offsets[i], sizes[i], granule,
+                                data + i * granule);
+        }
+        return status;
+      },
+      unpacked);
+}
+
+// Validation and plan of both calls; chunking as marked_stream_sync.
+// kIoOk with plan->marked == 0 means nothing to do.
+int lz_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
+            const std::vector<uint64_t>& bitmap, uint64_t staging_bytes,
+            bool have_callback, MarkedPlan* plan, std::string* error) {
+  if (!lz_granule_ok(granule)) {
+    if (error != nullptr) {
+      *error = "compression needs 512 <= granule <= 16384, a multiple of 16";
+    }
+    return kIoInvalid;
+  }
+  if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule,
+                         &bitmap) ||
+      (staging_bytes != 0 && staging_bytes < granule)) {
+    return kIoInvalid;
+  }
+  *plan = build_marked_plan(length / granule, bitmap, true);
+  if (plan->marked != 0 && !have_callback) return kIoInvalid;
+  const uint64_t half =
+      staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
+  plan->chunk_granules =
+      std::min(std::max<uint64_t>(1, half / granule), plan->marked);
+  return kIoOk;
+}
+
+}  // namespace
+
+int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
+                              uint32_t granule,
+                              const std::vector<uint64_t>& bitmap,
+                              uint64_t staging_bytes, const CompressSink& sink,
+                              uint64_t* packed_out, std::string* error) {
+  uint64_t unused = 0;
+  uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
+  *packed = 0;
+  try {
+    MarkedPlan plan;
+    const int status = lz_plan(src, src_offset, length, granule, bitmap,
+                               staging_bytes, static_cast<bool>(sink), &plan,
+                               error);
+    if (status != kIoOk || plan.marked == 0) return status;
+    const int device = granule_kernel_device(src, src);
+    if (device < 0) {
+      return compress_generic(src, src_offset, length, granule, bitmap,
+                              staging_bytes, sink, packed);
+    }
+    LzStream ls(device, src, src_offset, granule, plan, true);
+    return compress_gpu(ls, plan, sink, packed);
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
+}
+
+int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
+                                uint64_t length, uint32_t granule,
+                                const std::vector<uint64_t>& bitmap,
+                                uint64_t staging_bytes,
+                                const DecompressSource& source,
+                                uint64_t* unpacked_out, std::string* error) {
+  uint64_t unused = 0;
+  uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
+  *unpacked = 0;
+  try {
+    MarkedPlan plan;
+    const int status = lz_plan(dst, dst_offset, length, granule, bitmap,
+                               staging_bytes, static_cast<bool>(source), &plan,
+                               error);
+    if (status != kIoOk || plan.marked == 0) return status;
+    const int device = granule_kernel_device(dst, dst);
+    if (device < 0) {
+      return decompress_generic(dst, dst_offset, length, granule, bitmap,
+                                staging_bytes, source, unpacked, error);
+    }
+    LzStream ls(device, dst, dst_offset, granule, plan, false);
+    return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
+}
+
+}  // namespace hipstore

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "checked_file.h"
+#include "hipstore/compress.h"
 #include "hipstore/engine.h"
 #include "hipstore/fingerprint.h"
 
@@ -27,6 +28,9 @@ static_assert(kDeltaHeaderBytes == kHeaderBytes &&
 const Format kDelta = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
                        {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
                        kDeltaVersion, "delta file"};
+const Format kDeltaLz = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
+                         {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
+                         kDeltaVersionLz, "delta file"};
 const Format kMap = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
                      {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
                      kFingerprintMapVersion, "fingerprint map"};
@@ -76,6 +80,7 @@ struct ParsedDelta {
   DeltaInfo info;
   std::vector<uint64_t> bitmap;
   uint64_t records_offset = 0;
+  uint64_t record_area = 0;  // version 2
 };
 
 // The structural pass: everything that can be checked without reading
@@ -83,11 +88,12 @@ struct ParsedDelta {
 int parse_delta(const std::string& path, ParsedDelta* out,
                 std::string* error) {
   InFile& in = out->in;
-  int status = in.open(path, kDelta, error);
+  int status = in.open(path, kDelta, error, &kDeltaLz);
   if (status != kIoOk) return status;
   const Header& h = in.header;
   DeltaInfo& info = out->info;
-  info.version = kDeltaVersion;
+  info.version = in.format().version;
+  info.compressed = info.version == kDeltaVersionLz;
   info.block_size = h.block_size;
   info.granule = h.granule;
   info.full = (h.word & kDeltaFlagFull) != 0;
@@ -95,8 +101,9 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   info.n_granules = h.n_granules;
   info.n_marked = get_u64(h.owned);
   info.file_bytes = in.file_bytes;
-  if ((h.word & ~kDeltaFlagFull) != 0 || get_u32(h.owned + 12) != 0 ||
-      get_u32(h.owned + 16) != 0) {
+  if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz)) != 0 ||
+      ((h.word & kDeltaFlagLz) != 0) != info.compressed ||
+      (!info.compressed && get_u64(h.owned + 12) != 0)) {
     return fail(error, kIoInvalid, "unknown flags or non-zero reserved field");
   }
   if (!geometry_ok(h.block_size, h.granule, h.volume_bytes, h.n_granules) ||
@@ -105,10 +112,26 @@ int parse_delta(const std::string& path, ParsedDelta* out,
     return fail(error, kIoInvalid, "inconsistent geometry in header");
   }
   const uint64_t n_words = (info.n_granules + 63) / 64;
-  status = in.check_length(
-      n_words * 8 + record_stream_bytes(info.n_marked, info.granule,
-                                        record_granules(info.granule)),
-      error);
+  uint64_t records = record_stream_bytes(info.n_marked, info.granule,
+                                         record_granules(info.granule));
+  info.stored_bytes = info.n_marked * info.granule;
+  if (info.compressed) {
+    if (!lz_granule_ok(info.granule)) {
+      return fail(error, kIoInvalid, "granule outside the compressed range");
+    }
+    // Record heads and sizes, then 1 .. granule bytes per piece: with
+    // that, neither the length below nor stored_bytes wraps.
+    const uint64_t fixed =
+        (records - info.stored_bytes) * 2 + info.n_marked * 4;
+    out->record_area = get_u64(h.owned + 12);
+    if (out->record_area < fixed + info.n_marked ||
+        out->record_area > fixed + info.stored_bytes) {
+      return fail(error, kIoInvalid, "record_area_bytes out of range");
+    }
+    info.stored_bytes = out->record_area - fixed;
+    records = out->record_area;
+  }
+  status = in.check_length(n_words * 8 + records, error);
   if (status != kIoOk) return status;
   std::vector<uint8_t> raw(n_words * 8);
   if (!in.read(raw.data(), raw.size(), kHeaderBytes)) {
@@ -132,10 +155,58 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   return in.check_trailer(info.n_marked, error);
 }
 
+// The version-2 file: as write_delta, with the granules compressed
+// (bdev_compress_marked_sync) and record_area_bytes put into the header
+// once the records are out.
+int write_delta_lz(OutFile* out, Bdev* src,
+                   const std::vector<uint64_t>& bitmap, DeltaInfo* info,
+                   std::string* error) {
+  std::vector<uint8_t> raw(bitmap.size() * 8);
+  for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
+  Header h = {info->block_size, info->granule,
+              (info->full ? kDeltaFlagFull : 0) | kDeltaFlagLz,
+              info->volume_bytes, info->n_granules, {0}};
+  put_u64(h.owned, info->n_marked);
+  put_u32(h.owned + 8, crc32c_sw(0, raw.data(), raw.size()));
+  int status = out->begin(kDeltaLz, h, error);
+  if (status != kIoOk) return status;
+  VarRecordWriter writer(out, info->granule, record_granules(info->granule),
+                         info->n_marked);
+  if (out->write(raw.data(), raw.size())) {  // else end() reports it
+    uint64_t packed = 0;
+    std::string why;
+    status = bdev_compress_marked_sync(
+        src, 0, info->volume_bytes, info->granule, bitmap, 0,
+        [&writer](const uint8_t* data, const uint32_t* sizes, uint64_t,
+                  uint64_t count) {
+          int added = kIoOk;
+          for (uint64_t i = 0; i < count && added == kIoOk; ++i) {
+            added = writer.add(data, sizes[i]);
+            data += lz_padded(sizes[i]);
+          }
+          return added;
+        },
+        &packed, &why);
+    if (status != kIoOk || packed != info->n_marked || !writer.complete()) {
+      if (why.empty()) {
+        why = "reading the volume or writing " + out->tmp() + " failed";
+      }
+      return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed, why);
+    }
+    put_u64(h.owned + 12, writer.area());
+    out->rewrite_header(h);
+  }
+  status = out->end(info->n_marked, error);
+  info->file_bytes = out->bytes();
+  info->stored_bytes = writer.unit_bytes();
+  return status;
+}
+
 // Header, bitmap, the marked granules of `src` as records, trailer, all
-// synced. Fills info->file_bytes.
+// synced. Fills info->file_bytes and info->stored_bytes.
 int write_delta(OutFile* out, Bdev* src, const std::vector<uint64_t>& bitmap,
                 DeltaInfo* info, std::string* error) {
+  if (info->compressed) return write_delta_lz(out, src, bitmap, info, error);
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
   Header h = {info->block_size, info->granule,
@@ -162,6 +233,7 @@ int write_delta(OutFile* out, Bdev* src, const std::vector<uint64_t>& bitmap,
   }
   status = out->end(info->n_marked, error);
   info->file_bytes = out->bytes();
+  info->stored_bytes = info->n_marked * info->granule;
   return status;
 }
 
@@ -334,6 +406,65 @@ int mark_all(Bdev* src, uint32_t granule, Marked* out, std::string* error) {
   return kIoOk;
 }
 
+// The record pass of a version-2 import. dry_run validates every piece
+// here; otherwise bdev_decompress_marked_sync does, before it decodes.
+int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run, std::string* error) {
+  const DeltaInfo& info = file->info;
+  VarRecordReader reader(&file->in, file->records_offset, file->record_area,
+                         info.granule, record_granules(info.granule),
+                         info.n_marked);
+  std::string why;
+  int status = kIoOk;
+  const uint8_t* piece = nullptr;
+  uint32_t size = 0;
+  if (dry_run) {
+    for (uint64_t w = 0; w < file->bitmap.size() && status == kIoOk; ++w) {
+      for (uint64_t word = file->bitmap[w]; word != 0 && status == kIoOk;
+           word &= word - 1) {
+        status = reader.next(&piece, &size, &why);
+        std::string rule;
+        if (status == kIoOk &&
+            !lz_validate_granule(piece, size, info.granule, &rule)) {
+          status = kIoInvalid;
+          why = "granule " +
+                std::to_string(w * 64 +
+                               static_cast<uint64_t>(__builtin_ctzll(word))) +
+                ": bad compressed piece (" + rule + ")";
+        }
+      }
+    }
+    if (status != kIoOk) return fail(error, status, why);
+  } else if (info.n_marked > 0) {
+    uint64_t applied = 0;
+    status = bdev_decompress_marked_sync(
+        dst, 0, info.volume_bytes, info.granule, file->bitmap, 0,
+        [&](uint8_t* data, uint32_t* sizes, uint64_t, uint64_t count) {
+          for (uint64_t i = 0; i < count; ++i) {
+            const int got = reader.next(&piece, &size, &why);
+            if (got != kIoOk) return got;
+            sizes[i] = size;
+            memcpy(data, piece, size);
+            memset(data + size, 0, lz_padded(size) - size);
+            data += lz_padded(size);
+          }
+          return static_cast<int>(kIoOk);
+        },
+        &applied, &why);
+    if (status != kIoOk) {
+      if (why.empty()) why = "writing the target failed";
+      return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
+                  why + "; " + std::to_string(applied) + " of " +
+                      std::to_string(info.n_marked) +
+                      " granules were applied, the target may be partly "
+                      "updated");
+    }
+  }
+  if (reader.left() != 0) {
+    return fail(error, kIoInvalid, "records left over after the last granule");
+  }
+  return kIoOk;
+}
+
 }  // namespace
 
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
@@ -345,7 +476,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
 
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
-                      DeltaInfo* stats, std::string* error) {
+                      DeltaInfo* stats, std::string* error, bool compress) {
   if (src == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
   }
@@ -375,8 +506,14 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
     status = mark_all(src, granule, &marked, error);
   }
   if (status != kIoOk) return status;
+  if (compress && !lz_granule_ok(granule)) {
+    return fail(error, kIoInvalid,
+                "compress needs 512 <= granule <= 16384 (granule " +
+                    std::to_string(granule) + ")");
+  }
   DeltaInfo info;
-  info.version = kDeltaVersion;
+  info.version = compress ? kDeltaVersionLz : kDeltaVersion;
+  info.compressed = compress;
   info.block_size = static_cast<uint32_t>(src->block_size());
   info.granule = granule;
   info.full = base == nullptr && base_map.empty();
@@ -447,6 +584,11 @@ int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
     return fail(error, kIoFailed,
                 "bdev " + dst->name() +
                     " is claimed; import runs offline only");
+  }
+  if (info.compressed) {
+    status = import_lz(dst, &file, dry_run, error);
+    if (status == kIoOk && stats != nullptr) *stats = info;
+    return status;
   }
   RecordReader reader(&file.in, file.records_offset, info.granule,
                       record_granules(info.granule), info.n_marked);

@@ -1240,7 +1240,8 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
       "bdev_export_delta", [&manager, granule_param, delta_error](const Json& p) {
         // Writes a volume, or with "base" its difference from an earlier
         // clone, to a delta file (HBM volumes leave through
-        // k_pack_marked, one launch per staging window).
+        // k_pack_marked, one launch per staging window; with "compress"
+        // through k_lz_compress_marked and k_gather_var).
         const std::string name = p.get_string("name");
         BdevPtr src = manager.find(name);
         if (!src) not_found("bdev " + name);
@@ -1267,7 +1268,7 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         const int status =
             bdev_export_delta(src.get(), base.get(), path, granule,
                               p.get_bool("overwrite", false), &maps, &info,
-                              &why);
+                              &why, p.get_bool("compress", false));
         if (status != kIoOk) throw delta_error("bdev_export_delta", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));
@@ -1275,6 +1276,9 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         o["saved"] = Json(static_cast<int64_t>(info.n_marked));
         o["file_bytes"] = Json(static_cast<int64_t>(info.file_bytes));
         o["full"] = Json(info.full);
+        if (info.compressed) {
+          o["stored_bytes"] = Json(static_cast<int64_t>(info.stored_bytes));
+        }
         if (!maps.map_out.empty()) {
           o["map_bytes"] = Json(static_cast<int64_t>(maps.map_bytes));
         }

@@ -17,6 +17,7 @@
 #include "hipstore/bdev.h"
 #include "hipstore/composite.h"
 #include "hipstore/crc32c.h"
+#include "hipstore/compress.h"
 #include "hipstore/delta.h"
 #include "hipstore/engine.h"
 #include "hipstore/fingerprint.h"
@@ -177,6 +178,10 @@ py::dict delta_info_to_dict(const DeltaInfo& info) {
   d["granules"] = info.n_granules;
   d["marked"] = info.n_marked;
   d["file_bytes"] = info.file_bytes;
+  if (info.compressed) {  // version 1 keeps the keys it always had
+    d["compressed"] = true;
+    d["stored_bytes"] = info.stored_bytes;
+  }
   return d;
 }
 
@@ -628,7 +633,8 @@ PYBIND11_MODULE(_hipstore, m) {
                                 std::optional<uint32_t> granule,
                                 bool overwrite,
                                 std::optional<std::string> base_map,
-                                std::optional<std::string> map_out) {
+                                std::optional<std::string> map_out,
+                                bool compress) {
     DeltaInfo info;
     DeltaMaps maps;
     maps.base_map = base_map.value_or("");
@@ -636,7 +642,7 @@ PYBIND11_MODULE(_hipstore, m) {
     delta_call("bdev_export_delta", [&](std::string* error) {
       return bdev_export_delta(src.get(), base ? base->get() : nullptr, path,
                                granule.value_or(0), overwrite, &maps, &info,
-                               error);
+                               error, compress);
     });
     py::dict d = delta_info_to_dict(info);
     if (!maps.map_out.empty()) d["map_bytes"] = maps.map_bytes;
@@ -644,10 +650,127 @@ PYBIND11_MODULE(_hipstore, m) {
   }, py::arg("src"), py::arg("path"), py::arg("base") = py::none(),
      py::arg("granule") = py::none(), py::arg("overwrite") = false,
      py::arg("base_map") = py::none(), py::arg("map_out") = py::none(),
+     py::arg("compress") = false,
      "Write the granules of src that differ from base, or from the state "
      "recorded in the fingerprint map base_map (every granule without "
      "either), to a hipstore delta file; map_out also writes the "
-     "fingerprint map of src");
+     "fingerprint map of src; compress writes a version-2 file of HSLZ1 "
+     "pieces");
+
+  m.def("lz_compress_granule", [](py::bytes data) {
+    const std::string in = data;
+    if (!lz_granule_ok(in.size())) {
+      throw std::invalid_argument(
+          "lz_compress_granule: 512 <= length <= 16384, a multiple of 16");
+    }
+    std::string out(in.size(), '\0');
+    const uint32_t size = lz_compress_granule(
+        reinterpret_cast<const uint8_t*>(in.data()),
+        static_cast<uint32_t>(in.size()), reinterpret_cast<uint8_t*>(&out[0]));
+    out.resize(size);
+    return py::bytes(out);
+  }, py::arg("data"),
+     "The stored form of one granule: an LZ4 block, or the granule itself "
+     "when that would not be smaller (host codec, the byte model of "
+     "k_lz_compress_marked)");
+
+  m.def("lz_decompress_granule", [](py::bytes piece, uint32_t granule) {
+    const std::string in = piece;
+    std::string out(lz_granule_ok(granule) ? granule : 0, '\0');
+    std::string why;
+    if (!lz_decompress_granule(reinterpret_cast<const uint8_t*>(in.data()),
+                               in.size(), granule,
+                               reinterpret_cast<uint8_t*>(&out[0]), &why)) {
+      throw std::invalid_argument("lz_decompress_granule: " + why);
+    }
+    return py::bytes(out);
+  }, py::arg("piece"), py::arg("granule"),
+     "Decode one stored piece (host codec); ValueError for a malformed one");
+
+  m.def("lz_validate_granule", [](py::bytes piece, uint32_t granule) {
+    const std::string in = piece;
+    return lz_validate_granule(reinterpret_cast<const uint8_t*>(in.data()),
+                               in.size(), granule);
+  }, py::arg("piece"), py::arg("granule"),
+     "True when a stored piece passes the token walk import runs");
+
+  m.def("bdev_compress_marked", [](BdevPtr src, py::bytes bitmap,
+                                   uint32_t granule, uint64_t src_offset,
+                                   std::optional<uint64_t> length,
+                                   uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len = marked_range("bdev_compress_marked", *src, src_offset,
+                                      length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    std::vector<uint32_t> sizes;
+    std::string out;
+    delta_call("bdev_compress_marked", [&](std::string* error) {
+      return bdev_compress_marked_sync(
+          src.get(), src_offset, len, granule, words, staging_bytes,
+          [&](const uint8_t* data, const uint32_t* window, uint64_t,
+              uint64_t count) {
+            for (uint64_t i = 0; i < count; ++i) {
+              out.append(reinterpret_cast<const char*>(data), window[i]);
+              data += lz_padded(window[i]);
+            }
+            sizes.insert(sizes.end(), window, window + count);
+            return 0;
+          },
+          nullptr, error);
+    });
+    return py::make_tuple(sizes, py::bytes(out));
+  }, py::arg("src"), py::arg("bitmap"), py::arg("granule"),
+     py::arg("src_offset") = 0, py::arg("length") = py::none(),
+     py::arg("staging_bytes") = 0,
+     "Compress the granules marked in `bitmap`, ascending (on-GPU for HBM "
+     "bdevs): (stored sizes, the pieces back to back)");
+
+  m.def("bdev_decompress_marked", [](BdevPtr dst, py::bytes bitmap,
+                                     uint32_t granule,
+                                     std::vector<uint32_t> sizes,
+                                     py::bytes data, uint64_t dst_offset,
+                                     std::optional<uint64_t> length,
+                                     uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len = marked_range("bdev_decompress_marked", *dst,
+                                      dst_offset, length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    const std::string pieces = data;
+    // Where each piece starts; sizes that overrun `data` fail below.
+    std::vector<uint64_t> starts(sizes.size() + 1, 0);
+    for (size_t i = 0; i < sizes.size(); ++i) {
+      starts[i + 1] = starts[i] + sizes[i];
+    }
+    if (starts.back() != pieces.size()) {
+      throw std::invalid_argument(
+          "bdev_decompress_marked: sizes do not add up to the data length");
+    }
+    uint64_t unpacked = 0;
+    delta_call("bdev_decompress_marked", [&](std::string* error) {
+      return bdev_decompress_marked_sync(
+          dst.get(), dst_offset, len, granule, words, staging_bytes,
+          [&](uint8_t* out, uint32_t* window, uint64_t first_rank,
+              uint64_t count) {
+            if (first_rank + count > sizes.size()) return static_cast<int>(kIoInvalid);
+            for (uint64_t i = 0; i < count; ++i) {
+              const uint32_t size = sizes[first_rank + i];
+              window[i] = size;
+              if (size == 0 || size > granule) continue;  // refused after us
+              memcpy(out, pieces.data() + starts[first_rank + i], size);
+              memset(out + size, 0, lz_padded(size) - size);
+              out += lz_padded(size);
+            }
+            return 0;
+          },
+          &unpacked, error);
+    });
+    return unpacked;
+  }, py::arg("dst"), py::arg("bitmap"), py::arg("granule"), py::arg("sizes"),
+     py::arg("data"), py::arg("dst_offset") = 0, py::arg("length") = py::none(),
+     py::arg("staging_bytes") = 0,
+     "Decode the pieces of bdev_compress_marked into the granules marked in "
+     "`bitmap`; every piece is validated on the host first. Returns the "
+     "number written");
 
   m.def("bdev_import_delta", [](BdevPtr dst, const std::string& path,
                                 bool dry_run) {

@@ -83,6 +83,9 @@ def main(argv=None) -> int:
             cmd.add_argument("--map-out", default="",
                              help="also write the volume's fingerprint map")
             cmd.add_argument("--overwrite", action="store_true")
+            cmd.add_argument("--compress", action="store_true",
+                             help="store every granule LZ-compressed "
+                             "(restore reads either kind of file)")
         if name == "restore":
             cmd.add_argument("--dry-run", action="store_true",
                              help="check the file, write nothing")
@@ -167,7 +170,8 @@ def main(argv=None) -> int:
                     spec.CheckpointMallocBDevRequest(
                         bdev_name=args.volume, base_name=args.base,
                         path=args.path, overwrite=args.overwrite,
-                        base_map=args.base_map, map_out=args.map_out),
+                        base_map=args.base_map, map_out=args.map_out,
+                        compress=args.compress),
                     metadata=metadata, timeout=600)
                 print(f"checkpointed {args.volume} -> {args.path}: "
                       f"{reply.saved} of {reply.granules} granules, "

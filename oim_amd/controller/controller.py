@@ -417,7 +417,8 @@ class Controller(spec.ControllerServicer):
                         client, name, path, base=base or None,
                         overwrite=request.overwrite,
                         base_map=request.base_map or None,
-                        map_out=request.map_out or None)
+                        map_out=request.map_out or None,
+                        compress=request.compress)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.CheckpointMallocBDevReply(

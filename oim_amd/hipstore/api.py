@@ -337,16 +337,20 @@ def bdev_export_delta(client: Client, name: str, path: str,
                       granule: Optional[int] = None,
                       overwrite: bool = False,
                       base_map: Optional[str] = None,
-                      map_out: Optional[str] = None) -> Dict:
+                      map_out: Optional[str] = None,
+                      compress: bool = False) -> Dict:
     """Checkpoint a volume to a delta file: every granule, or with
     `base` (an earlier clone) or `base_map` (the fingerprint map written
     with an earlier checkpoint; no clone needed) only the granules that
     differ from that state. `map_out` also writes the volume's
-    fingerprint map, the base_map of the next checkpoint.
+    fingerprint map, the base_map of the next checkpoint. `compress`
+    stores every granule LZ-compressed (a version-2 file; granules of
+    512 to 16384 bytes); bdev_import_delta reads either version.
 
-    Returns {granule, granules, saved, file_bytes, full} and, with
-    map_out, map_bytes. granule defaults to the block size, with
-    base_map to the map's."""
+    Returns {granule, granules, saved, file_bytes, full}, with map_out
+    also map_bytes and with compress stored_bytes (the bytes the granules
+    take in the file). granule defaults to the block size,
+    with base_map to the map's."""
     params: Dict = {"name": name, "path": path}
     if base is not None:
         params["base"] = base
@@ -358,6 +362,8 @@ def bdev_export_delta(client: Client, name: str, path: str,
         params["granule"] = granule
     if overwrite:
         params["overwrite"] = True
+    if compress:
+        params["compress"] = True
     return client.invoke("bdev_export_delta", params)
 
 

@@ -74,7 +74,8 @@ MESSAGES = [
     Message("CheckpointMallocBDevRequest",
             [Field("bdev_name", 1, "string"), Field("base_name", 2, "string"),
              Field("path", 3, "string"), Field("overwrite", 4, "bool"),
-             Field("base_map", 5, "string"), Field("map_out", 6, "string")]),
+             Field("base_map", 5, "string"), Field("map_out", 6, "string"),
+             Field("compress", 7, "bool")]),
     Message("CheckpointMallocBDevReply",
             [Field("granules", 1, "int64"), Field("saved", 2, "int64"),
              Field("file_bytes", 3, "int64")]),
