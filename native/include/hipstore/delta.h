@@ -32,6 +32,20 @@
 // Import tells the versions apart by itself. A version-2 record's CRC,
 // its sizes and then every piece (lz_validate_granule) are checked
 // before a byte of it is decoded or reaches the GPU.
+//
+// "hipstore delta file, version 3" holds the same granules encrypted
+// (HSXTS1, crypt.h; the data unit is the granule and its number the
+// granule's index in the volume) and is what an export with a key
+// writes. XTS preserves length, so it is the version-1 layout with three
+// differences:
+//   - version = 3 and flags bit 2 (kDeltaFlagXts) set; one implies the other
+//   - the first spare header word is xts_kcv(key), the second stays 0
+//   - record payloads are ciphertext
+// Record CRCs, the bitmap CRC and the exact-length rule are computed over
+// the file as stored, so the structural pass and a dry run need no key.
+// There is no authentication (a CRC is not a MAC), and a key together
+// with `compress` is refused: compress-then-encrypt needs padding or
+// ciphertext stealing.
 
 #pragma once
 
@@ -46,7 +60,9 @@ namespace hipstore {
 constexpr uint32_t kDeltaVersion = 1;
 constexpr uint32_t kDeltaVersionLz = 2;
 constexpr uint32_t kDeltaFlagFull = 1;
+constexpr uint32_t kDeltaVersionXts = 3;
 constexpr uint32_t kDeltaFlagLz = 2;
+constexpr uint32_t kDeltaFlagXts = 4;
 constexpr uint64_t kDeltaHeaderBytes = 64;
 constexpr uint64_t kDeltaTrailerBytes = 16;
 constexpr uint64_t kDeltaRecordBytes = 1ull << 20;
@@ -64,6 +80,7 @@ struct DeltaInfo {
   // Bytes the granules take in the file: n_marked * granule, or the sum
   // of the stored sizes of a compressed file.
   uint64_t stored_bytes = 0;
+  bool encrypted = false;  // version 3
 };
 
 // Every call returns an IoStatus and, on failure, a one-line reason in
@@ -89,8 +106,15 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
 // on. A bad record stops the import with the target partly updated.
 // dry_run runs every check and writes nothing. A claimed target is
 // refused.
+//
+// `key` (the 64 bytes of crypt.h) is required for a version-3 file and
+// kIoInvalid for any other; a key whose xts_kcv differs from the header's
+// is kIoInvalid before the target is touched. dry_run of a version-3
+// file works without a key (structure and CRCs, so a file can be vetted
+// where the key is not) and with one also checks the kcv.
 int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
-                      DeltaInfo* stats, std::string* error);
+                      DeltaInfo* stats, std::string* error,
+                      const std::vector<uint8_t>* key = nullptr);
 
 // Header fields of a file after the structural pass.
 int delta_file_info(const std::string& path, DeltaInfo* info,
@@ -177,6 +201,10 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
 // `compress` writes a version-2 file; the granule must then satisfy
 // lz_granule_ok (kIoInvalid otherwise). Maps are unaffected: they
 // describe the volume, not the file.
+//
+// `key` writes a version-3 file (granule <= 2^24; a key of another
+// length, with equal halves, or together with `compress` is kIoInvalid).
+// `base`, `base_map` and `map_out` work unchanged with it.
 struct DeltaMaps {
   std::string base_map;
   std::string map_out;
@@ -185,6 +213,7 @@ struct DeltaMaps {
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
                       DeltaInfo* stats, std::string* error,
-                      bool compress = false);
+                      bool compress = false,
+                      const std::vector<uint8_t>* key = nullptr);
 
 }  // namespace hipstore

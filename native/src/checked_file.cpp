@@ -49,7 +49,8 @@ uint64_t record_stream_bytes(uint64_t total, uint64_t unit,
 }
 
 int InFile::open(const std::string& path, const Format& format,
-                 std::string* error, const Format* newer) {
+                 std::string* error, const Format* newer,
+                 const Format* newest) {
   format_ = &format;
   in_.fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
   if (in_.fd < 0) return fail(error, kIoFailed, errno_text("open " + path));
@@ -74,6 +75,8 @@ int InFile::open(const std::string& path, const Format& format,
   }
   if (newer != nullptr && get_u32(h + 8) == newer->version) {
     format_ = newer;
+  } else if (newest != nullptr && get_u32(h + 8) == newest->version) {
+    format_ = newest;
   } else if (get_u32(h + 8) != format.version) {
     return fail(error, kIoInvalid, "unsupported " + noun + " version");
   }

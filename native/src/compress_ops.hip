@@ -55,42 +55,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ uint32_t uniform(uint32_t v) {
-  return __builtin_amdgcn_readfirstlane(v);
-}
-
-// fn(granule index, window slot) once per marked granule of the window,
-// by one wave. Unlike marked_window_walk (bulk_ops.hip), which gives a
-// workgroup a whole bitmap word, this walk gives every granule of the
-// window's words a wave of its own, grid-stride: a 16 MiB window of
-// 4 KiB granules is 64 words, and 64 workgroups leave most of the chip
-// idle under kernels that are bound by the latency of their serial
-// parse, not by bandwidth. The slot is the same pure function of the
-// bitmap and rank_before_word.
-template <typename Fn>
-__device__ __forceinline__ void lz_window_walk(
-    const unsigned long long* __restrict__ bitmap,
-    const uint32_t* __restrict__ rank_before_word, const MarkedWindow win,
-    Fn fn) {
-  const uint32_t n_waves = blockDim.x >> 6;
-  const uint64_t g_first = win.g_begin & ~63ull;
-  const uint64_t span = ((win.g_end + 63) & ~63ull) - g_first;
-  for (uint64_t v = static_cast<uint64_t>(blockIdx.x) * n_waves +
-                    uniform(threadIdx.x >> 6);
-       v < span; v += static_cast<uint64_t>(gridDim.x) * n_waves) {
-    const uint64_t g = g_first + v;  // wave-uniform, like all below
-    if (g < win.g_begin || g >= win.g_end) continue;
-    const unsigned long long word = bitmap[g >> 6];
-    const uint32_t bit = static_cast<uint32_t>(g & 63);
-    if (((word >> bit) & 1) == 0) continue;
-    const uint32_t slot =
-        uniform(rank_before_word[g >> 6]) - win.first_rank +
-        static_cast<uint32_t>(__popcll(word & ((1ull << bit) - 1)));
-    if (slot >= win.count) continue;  // bitmap and ranks disagree: stay inside
-    fn(g, slot);
-  }
-}
-
 // Little-endian u32 at byte `q` of an LDS image, q + 8 <= its size:
 // two aligned words and a funnel shift.
 __device__ __forceinline__ uint32_t lds_u32(const uint32_t* img, uint32_t q) {
@@ -224,7 +188,8 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_compress_marked(
                 (threadIdx.x >> 6) * (2 * granule + kLzTableBytes);
   uint8_t* out = in + granule;
   uint32_t* table = reinterpret_cast<uint32_t*>(out + granule);
-  lz_window_walk(bitmap, rank_before_word, win, [&](uint64_t g, uint32_t slot) {
+  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
+                                                      uint32_t slot) {
     const uint4* __restrict__ pg =
         reinterpret_cast<const uint4*>(src + g * granule);
     uint4* in16 = reinterpret_cast<uint4*>(in);
@@ -348,7 +313,8 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
   const uint32_t n16 = granule >> 4;
   uint4* piece16 = lz_lds + (threadIdx.x >> 6) * (2 * n16);
   uint4* image16 = piece16 + n16;
-  lz_window_walk(bitmap, rank_before_word, win, [&](uint64_t g, uint32_t slot) {
+  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
+                                                      uint32_t slot) {
     const uint32_t size = uniform(sizes[slot]);
     const uint4* __restrict__ pp =
         reinterpret_cast<const uint4*>(dense + offsets[slot]);
@@ -380,14 +346,6 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
 // Waves per workgroup for `per_wave` bytes of LDS each.
 uint32_t lz_waves(uint32_t per_wave) {
   return 4 * per_wave <= kLzMaxLds ? 4 : 2 * per_wave <= kLzMaxLds ? 2 : 1;
-}
-
-// Workgroups of `waves` waves for lz_window_walk: a wave per granule of
-// the window's bitmap words, at most 2048.
-uint32_t lz_window_grid(const MarkedWindow& win, uint32_t waves) {
-  const uint64_t span = (win.g_end + 63) / 64 * 64 - win.g_begin / 64 * 64;
-  return static_cast<uint32_t>(
-      std::min<uint64_t>((span + waves - 1) / waves, 2048));
 }
 
 // Device memory that grows on demand and keeps what it has, like
@@ -522,7 +480,7 @@ struct LzStream : HalvesStream {
   void compress(const MarkedWindow& win, int half) {
     const uint32_t per_wave = 2 * granule + kLzTableBytes;
     const uint32_t waves = lz_waves(per_wave);
-    hipLaunchKernelGGL(k_lz_compress_marked, dim3(lz_window_grid(win, waves)),
+    hipLaunchKernelGGL(k_lz_compress_marked, dim3(wave_window_grid(win, waves)),
                        dim3(waves * 64), waves * per_wave, stream, base,
                        scratch + half * chunk * granule,
                        device_view(sizes + half * chunk), dev_words, dev_ranks,
@@ -549,7 +507,7 @@ struct LzStream : HalvesStream {
     const uint32_t per_wave = 2 * granule;
     const uint32_t waves = lz_waves(per_wave);
     hipLaunchKernelGGL(k_lz_decompress_marked,
-                       dim3(lz_window_grid(win, waves)),
+                       dim3(wave_window_grid(win, waves)),
                        dim3(waves * 64), waves * per_wave, stream, base,
                        device_view(dense + half * chunk * granule),
                        device_view(sizes + half * chunk),

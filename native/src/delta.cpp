@@ -12,6 +12,7 @@
 
 #include "checked_file.h"
 #include "hipstore/compress.h"
+#include "hipstore/crypt.h"
 #include "hipstore/engine.h"
 #include "hipstore/fingerprint.h"
 
@@ -31,6 +32,9 @@ const Format kDelta = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
 const Format kDeltaLz = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
                          {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
                          kDeltaVersionLz, "delta file"};
+const Format kDeltaXts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
+                          {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
+                          kDeltaVersionXts, "delta file"};
 const Format kMap = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
                      {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
                      kFingerprintMapVersion, "fingerprint map"};
@@ -81,6 +85,7 @@ struct ParsedDelta {
   std::vector<uint64_t> bitmap;
   uint64_t records_offset = 0;
   uint64_t record_area = 0;  // version 2
+  uint32_t kcv = 0;          // version 3
 };
 
 // The structural pass: everything that can be checked without reading
@@ -88,12 +93,13 @@ struct ParsedDelta {
 int parse_delta(const std::string& path, ParsedDelta* out,
                 std::string* error) {
   InFile& in = out->in;
-  int status = in.open(path, kDelta, error, &kDeltaLz);
+  int status = in.open(path, kDelta, error, &kDeltaLz, &kDeltaXts);
   if (status != kIoOk) return status;
   const Header& h = in.header;
   DeltaInfo& info = out->info;
   info.version = in.format().version;
   info.compressed = info.version == kDeltaVersionLz;
+  info.encrypted = info.version == kDeltaVersionXts;
   info.block_size = h.block_size;
   info.granule = h.granule;
   info.full = (h.word & kDeltaFlagFull) != 0;
@@ -101,10 +107,19 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   info.n_granules = h.n_granules;
   info.n_marked = get_u64(h.owned);
   info.file_bytes = in.file_bytes;
-  if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz)) != 0 ||
+  // The spare words: version 1 none, version 2 both, version 3 the first.
+  if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz | kDeltaFlagXts)) != 0 ||
       ((h.word & kDeltaFlagLz) != 0) != info.compressed ||
-      (!info.compressed && get_u64(h.owned + 12) != 0)) {
+      ((h.word & kDeltaFlagXts) != 0) != info.encrypted ||
+      (!info.compressed && get_u32(h.owned + 16) != 0) ||
+      (!info.compressed && !info.encrypted && get_u32(h.owned + 12) != 0)) {
     return fail(error, kIoInvalid, "unknown flags or non-zero reserved field");
+  }
+  if (info.encrypted) {
+    if (!xts_granule_ok(info.granule)) {
+      return fail(error, kIoInvalid, "granule outside the encrypted range");
+    }
+    out->kcv = get_u32(h.owned + 12);
   }
   if (!geometry_ok(h.block_size, h.granule, h.volume_bytes, h.n_granules) ||
       info.n_marked > info.n_granules ||
@@ -203,29 +218,40 @@ int write_delta_lz(OutFile* out, Bdev* src,
 }
 
 // Header, bitmap, the marked granules of `src` as records, trailer, all
-// synced. Fills info->file_bytes and info->stored_bytes.
+// synced. Fills info->file_bytes and info->stored_bytes. With `key`
+// (info->encrypted) the records hold what bdev_xts_pack_marked_sync
+// delivers and the header the key check value.
 int write_delta(OutFile* out, Bdev* src, const std::vector<uint64_t>& bitmap,
-                DeltaInfo* info, std::string* error) {
+                const std::vector<uint8_t>* key, DeltaInfo* info,
+                std::string* error) {
   if (info->compressed) return write_delta_lz(out, src, bitmap, info, error);
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
   Header h = {info->block_size, info->granule,
-              info->full ? kDeltaFlagFull : 0, info->volume_bytes,
-              info->n_granules, {0}};
+              (info->full ? kDeltaFlagFull : 0) |
+                  (info->encrypted ? kDeltaFlagXts : 0),
+              info->volume_bytes, info->n_granules, {0}};
   put_u64(h.owned, info->n_marked);
   put_u32(h.owned + 8, crc32c_sw(0, raw.data(), raw.size()));
-  int status = out->begin(kDelta, h, error);
+  if (info->encrypted) put_u32(h.owned + 12, xts_kcv(key->data()));
+  int status = out->begin(info->encrypted ? kDeltaXts : kDelta, h, error);
   if (status != kIoOk) return status;
   if (out->write(raw.data(), raw.size())) {  // else end() reports it
     RecordWriter writer(out, info->granule, record_granules(info->granule),
                         info->n_marked);
     uint64_t packed = 0;
-    status = bdev_pack_marked_sync(
-        src, 0, info->volume_bytes, info->granule, bitmap, 0,
-        [&writer](const uint8_t* data, uint64_t, uint64_t count) {
-          return writer.add(data, count);
-        },
-        &packed);
+    const PackSink sink = [&writer](const uint8_t* data, uint64_t,
+                                    uint64_t count) {
+      return writer.add(data, count);
+    };
+    status = info->encrypted
+                 ? bdev_xts_pack_marked_sync(src, 0, info->volume_bytes,
+                                             info->granule, bitmap,
+                                             key->data(), key->size(), 0, 0,
+                                             sink, &packed)
+                 : bdev_pack_marked_sync(src, 0, info->volume_bytes,
+                                         info->granule, bitmap, 0, sink,
+                                         &packed);
     if (status != kIoOk || packed != info->n_marked || !writer.complete()) {
       return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
                   "reading the volume or writing " + out->tmp() + " failed");
@@ -476,9 +502,17 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
 
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
-                      DeltaInfo* stats, std::string* error, bool compress) {
+                      DeltaInfo* stats, std::string* error, bool compress,
+                      const std::vector<uint8_t>* key) {
   if (src == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
+  }
+  if (key != nullptr && !xts_key_ok(key->data(), key->size())) {
+    return fail(error, kIoInvalid,
+                "the key must be 64 bytes whose halves differ");
+  }
+  if (key != nullptr && compress) {
+    return fail(error, kIoInvalid, "key and compress exclude each other");
   }
   const std::string base_map = maps != nullptr ? maps->base_map : "";
   const std::string map_out = maps != nullptr ? maps->map_out : "";
@@ -511,9 +545,15 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                 "compress needs 512 <= granule <= 16384 (granule " +
                     std::to_string(granule) + ")");
   }
+  if (key != nullptr && !xts_granule_ok(granule)) {
+    return fail(error, kIoInvalid, "a key needs granule <= 16777216");
+  }
   DeltaInfo info;
-  info.version = compress ? kDeltaVersionLz : kDeltaVersion;
+  info.version = compress        ? kDeltaVersionLz
+                 : key != nullptr ? kDeltaVersionXts
+                                  : kDeltaVersion;
   info.compressed = compress;
+  info.encrypted = key != nullptr;
   info.block_size = static_cast<uint32_t>(src->block_size());
   info.granule = granule;
   info.full = base == nullptr && base_map.empty();
@@ -539,7 +579,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   OutFile delta(path);
   OutFile map(map_out);
   FingerprintMapInfo map_info;
-  status = write_delta(&delta, src, marked.bitmap, &info, error);
+  status = write_delta(&delta, src, marked.bitmap, key, &info, error);
   if (status == kIoOk && !map_out.empty()) {
     status = write_map(&map, src->block_size(), granule, info.volume_bytes,
                        marked.fps, &map_info, error);
@@ -564,14 +604,29 @@ int delta_file_info(const std::string& path, DeltaInfo* info,
 }
 
 int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
-                      DeltaInfo* stats, std::string* error) {
+                      DeltaInfo* stats, std::string* error,
+                      const std::vector<uint8_t>* key) {
   if (dst == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
+  }
+  if (key != nullptr && !xts_key_ok(key->data(), key->size())) {
+    return fail(error, kIoInvalid,
+                "the key must be 64 bytes whose halves differ");
   }
   ParsedDelta file;
   int status = parse_delta(path, &file, error);
   if (status != kIoOk) return status;
   const DeltaInfo& info = file.info;
+  if (key != nullptr && !info.encrypted) {
+    return fail(error, kIoInvalid, "a key was given for an unencrypted file");
+  }
+  if (info.encrypted && key == nullptr && !dry_run) {
+    return fail(error, kIoInvalid, "the file is encrypted: a key is required");
+  }
+  if (key != nullptr && xts_kcv(key->data()) != file.kcv) {
+    return fail(error, kIoInvalid,
+                "wrong key (key check value differs from the file's)");
+  }
   if (info.block_size != dst->block_size()) {
     return fail(error, kIoInvalid,
                 "file block size " + std::to_string(info.block_size) +
@@ -598,12 +653,18 @@ int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
     if (status != kIoOk) return fail(error, status, why);
   } else if (info.n_marked > 0) {
     uint64_t applied = 0;
-    status = bdev_unpack_marked_sync(
-        dst, 0, info.volume_bytes, info.granule, file.bitmap, 0,
-        [&reader, &why](uint8_t* data, uint64_t, uint64_t count) {
-          return reader.take(data, count, &why);
-        },
-        &applied);
+    const UnpackSource source = [&reader, &why](uint8_t* data, uint64_t,
+                                                uint64_t count) {
+      return reader.take(data, count, &why);
+    };
+    status = info.encrypted
+                 ? bdev_xts_unpack_marked_sync(dst, 0, info.volume_bytes,
+                                               info.granule, file.bitmap,
+                                               key->data(), key->size(), 0, 0,
+                                               source, &applied)
+                 : bdev_unpack_marked_sync(dst, 0, info.volume_bytes,
+                                           info.granule, file.bitmap, 0,
+                                           source, &applied);
     if (status != kIoOk) {
       if (why.empty()) why = "writing the target failed";
       return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,

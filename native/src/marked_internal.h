@@ -1,9 +1,11 @@
 // Private to native/src: what the calls that walk a bitmap of marked
 // granules window by window have in common. bulk_ops.hip (pack / unpack)
-// defines the functions; compress_ops.hip (LZ compress / decompress)
-// uses them, so both cut the same windows from the same plan.
+// defines the functions; compress_ops.hip (LZ compress / decompress) and
+// crypt_ops.hip (XTS pack / unpack) use them, so all cut the same windows
+// from the same plan, and share the wave-per-granule walk below.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -70,6 +72,50 @@ inline uint32_t marked_window_grid(const MarkedWindow& win) {
 // Internal linkage because its base is (gpu_internal.h gives every
 // translation unit its own ScopedStream).
 namespace {
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) {
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
+// fn(granule index, window slot) once per marked granule of the window,
+// by one wave. Unlike marked_window_walk (bulk_ops.hip), which gives a
+// workgroup a whole bitmap word, this walk gives every granule of the
+// window's words a wave of its own, grid-stride: a 16 MiB window of
+// 4 KiB granules is 64 words, and 64 workgroups leave most of the chip
+// idle under kernels that are bound by arithmetic or by the latency of a
+// serial parse, not by bandwidth (compress_ops.hip, crypt_ops.hip). The
+// slot is the same pure function of the bitmap and rank_before_word.
+template <typename Fn>
+__device__ __forceinline__ void wave_window_walk(
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, const MarkedWindow win,
+    Fn fn) {
+  const uint32_t n_waves = blockDim.x >> 6;
+  const uint64_t g_first = win.g_begin & ~63ull;
+  const uint64_t span = ((win.g_end + 63) & ~63ull) - g_first;
+  for (uint64_t v = static_cast<uint64_t>(blockIdx.x) * n_waves +
+                    uniform(threadIdx.x >> 6);
+       v < span; v += static_cast<uint64_t>(gridDim.x) * n_waves) {
+    const uint64_t g = g_first + v;  // wave-uniform, like all below
+    if (g < win.g_begin || g >= win.g_end) continue;
+    const unsigned long long word = bitmap[g >> 6];
+    const uint32_t bit = static_cast<uint32_t>(g & 63);
+    if (((word >> bit) & 1) == 0) continue;
+    const uint32_t slot =
+        uniform(rank_before_word[g >> 6]) - win.first_rank +
+        static_cast<uint32_t>(__popcll(word & ((1ull << bit) - 1)));
+    if (slot >= win.count) continue;  // bitmap and ranks disagree: stay inside
+    fn(g, slot);
+  }
+}
+
+// Workgroups of `waves` waves for wave_window_walk: a wave per granule of
+// the window's bitmap words, at most 2048.
+inline uint32_t wave_window_grid(const MarkedWindow& win, uint32_t waves) {
+  const uint64_t span = (win.g_end + 63) / 64 * 64 - win.g_begin / 64 * 64;
+  return static_cast<uint32_t>(
+      std::min<uint64_t>((span + waves - 1) / waves, 2048));
+}
 
 // A one-shot stream with one event per half of a two-half pinned
 // buffer: the window loops launch into one half while the host works on

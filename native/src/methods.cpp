@@ -6,6 +6,10 @@
 // kInvalidParams like SPDK does; all reference callers tolerate that
 // (reference local.go:53-57, controller.go:76,204,239).
 
+#include <fcntl.h>
+#include <string.h>
+#include <unistd.h>
+
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
@@ -15,6 +19,7 @@
 
 #include "hipstore/bdev.h"
 #include "hipstore/composite.h"
+#include "hipstore/crypt.h"
 #include "hipstore/delta.h"
 #include "hipstore/engine.h"
 #include "hipstore/json.h"
@@ -1236,12 +1241,48 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
                     std::string(method) + ": " + why};
   };
 
+  // "key_file": a path the daemon reads, exactly 64 raw bytes (crypt.h).
+  // Key bytes never travel in a request, a reply, a log line or
+  // save_config; the copy here is cleared when the call ends.
+  struct KeyFile {
+    std::vector<uint8_t> bytes;
+    bool given = false;
+    ~KeyFile() {
+      if (!bytes.empty()) explicit_bzero(bytes.data(), bytes.size());
+    }
+    const std::vector<uint8_t>* ptr() const { return given ? &bytes : nullptr; }
+  };
+  auto read_key_file = [](const Json& p, KeyFile* key) {
+    if (!p.has("key_file")) return;
+    const std::string path = p.get_string("key_file");
+    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (fd < 0) {
+      throw RpcError{kInvalidParams, "key_file: cannot open " + path};
+    }
+    key->bytes.assign(kXtsKeyBytes + 1, 0);
+    size_t got = 0;
+    for (ssize_t n; got < key->bytes.size() &&
+                    (n = ::read(fd, key->bytes.data() + got,
+                                key->bytes.size() - got)) > 0;) {
+      got += static_cast<size_t>(n);
+    }
+    ::close(fd);
+    key->given = true;
+    if (got != kXtsKeyBytes) {
+      throw RpcError{kInvalidParams,
+                     "key_file: " + path + " must hold exactly 64 bytes"};
+    }
+    key->bytes.resize(kXtsKeyBytes);
+  };
+
   server->register_method(
-      "bdev_export_delta", [&manager, granule_param, delta_error](const Json& p) {
+      "bdev_export_delta",
+      [&manager, granule_param, delta_error, read_key_file](const Json& p) {
         // Writes a volume, or with "base" its difference from an earlier
         // clone, to a delta file (HBM volumes leave through
         // k_pack_marked, one launch per staging window; with "compress"
-        // through k_lz_compress_marked and k_gather_var).
+        // through k_lz_compress_marked and k_gather_var, with "key_file"
+        // through k_xts_pack_marked).
         const std::string name = p.get_string("name");
         BdevPtr src = manager.find(name);
         if (!src) not_found("bdev " + name);
@@ -1263,12 +1304,14 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         const uint32_t granule =
             !maps.base_map.empty() && !p.has("granule") ? 0
                                                         : granule_param(p, src);
+        KeyFile key;
+        read_key_file(p, &key);
         DeltaInfo info;
         std::string why;
         const int status =
             bdev_export_delta(src.get(), base.get(), path, granule,
                               p.get_bool("overwrite", false), &maps, &info,
-                              &why, p.get_bool("compress", false));
+                              &why, p.get_bool("compress", false), key.ptr());
         if (status != kIoOk) throw delta_error("bdev_export_delta", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));
@@ -1279,6 +1322,7 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         if (info.compressed) {
           o["stored_bytes"] = Json(static_cast<int64_t>(info.stored_bytes));
         }
+        if (info.encrypted) o["encrypted"] = Json(true);
         if (!maps.map_out.empty()) {
           o["map_bytes"] = Json(static_cast<int64_t>(maps.map_bytes));
         }
@@ -1334,18 +1378,23 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
       });
 
   server->register_method(
-      "bdev_import_delta", [&manager, delta_error](const Json& p) {
+      "bdev_import_delta",
+      [&manager, delta_error, read_key_file](const Json& p) {
         // Applies a delta file to a volume; offline only, like repair
-        // and resize. dry_run checks every CRC and writes nothing.
+        // and resize. dry_run checks every CRC and writes nothing. An
+        // encrypted file needs "key_file" (dry_run works without).
         const std::string name = p.get_string("name");
         BdevPtr dst = manager.find(name);
         if (!dst) not_found("bdev " + name);
         const std::string path = p.get_string("path");
         if (path.empty()) throw RpcError{kInvalidParams, "path required"};
+        KeyFile key;
+        read_key_file(p, &key);
         DeltaInfo info;
         std::string why;
-        const int status = bdev_import_delta(
-            dst.get(), path, p.get_bool("dry_run", false), &info, &why);
+        const int status =
+            bdev_import_delta(dst.get(), path, p.get_bool("dry_run", false),
+                              &info, &why, key.ptr());
         if (status != kIoOk) throw delta_error("bdev_import_delta", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));

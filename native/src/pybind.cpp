@@ -11,6 +11,7 @@
 
 #include <cstring>
 #include <numeric>
+#include <chrono>
 #include <optional>
 #include <stdexcept>
 
@@ -18,6 +19,7 @@
 #include "hipstore/composite.h"
 #include "hipstore/crc32c.h"
 #include "hipstore/compress.h"
+#include "hipstore/crypt.h"
 #include "hipstore/delta.h"
 #include "hipstore/engine.h"
 #include "hipstore/fingerprint.h"
@@ -182,7 +184,54 @@ py::dict delta_info_to_dict(const DeltaInfo& info) {
     d["compressed"] = true;
     d["stored_bytes"] = info.stored_bytes;
   }
+  if (info.encrypted) d["encrypted"] = true;
   return d;
+}
+
+// A key argument of the delta bindings: None = no key. Any length gets
+// through; the core refuses what is not an HSXTS1 key.
+struct KeyArg {
+  std::vector<uint8_t> bytes;
+  bool given = false;
+
+  explicit KeyArg(const std::optional<py::bytes>& key) : given(key.has_value()) {
+    if (given) {
+      const std::string raw = *key;
+      bytes.assign(raw.begin(), raw.end());
+    }
+  }
+  ~KeyArg() {
+    if (!bytes.empty()) explicit_bzero(bytes.data(), bytes.size());
+  }
+  const std::vector<uint8_t>* ptr() const { return given ? &bytes : nullptr; }
+};
+
+// Marks of `words` below granule n_granules.
+uint64_t marks_below(const std::vector<uint64_t>& words, uint64_t n_granules) {
+  uint64_t marked = 0;
+  for (uint64_t w = 0; w < n_granules / 64; ++w) {
+    marked += static_cast<uint64_t>(__builtin_popcountll(words[w]));
+  }
+  if (n_granules % 64 != 0) {
+    marked += static_cast<uint64_t>(__builtin_popcountll(
+        words[n_granules / 64] & ((1ull << (n_granules % 64)) - 1)));
+  }
+  return marked;
+}
+
+// The whole-granule argument of the host codec bindings.
+void check_units(const char* what, const std::string& data, uint32_t granule,
+                 const std::string& key) {
+  if (!xts_granule_ok(granule) || data.size() % granule != 0) {
+    throw std::invalid_argument(std::string(what) +
+                                ": granule must be a multiple of 16, at most "
+                                "2^24, that divides the data length");
+  }
+  if (!xts_key_ok(reinterpret_cast<const uint8_t*>(key.data()), key.size())) {
+    throw std::invalid_argument(std::string(what) +
+                                ": the key must be 64 bytes whose halves "
+                                "differ");
+  }
 }
 
 py::dict map_info_to_dict(const FingerprintMapInfo& info) {
@@ -562,16 +611,7 @@ PYBIND11_MODULE(_hipstore, m) {
     const std::vector<uint64_t> words = bitmap_words(raw);
     const std::string dense = data;
     if (granule != 0) {
-      // Marks below len / granule: whole words, then the masked last one.
-      const uint64_t n_granules = len / granule;
-      uint64_t marked = 0;
-      for (uint64_t w = 0; w < n_granules / 64; ++w) {
-        marked += static_cast<uint64_t>(__builtin_popcountll(words[w]));
-      }
-      if (n_granules % 64 != 0) {
-        marked += static_cast<uint64_t>(__builtin_popcountll(
-            words[n_granules / 64] & ((1ull << (n_granules % 64)) - 1)));
-      }
+      const uint64_t marked = marks_below(words, len / granule);
       if (dense.size() != marked * granule) {
         throw std::runtime_error(
             "bdev_unpack_marked: data length " + std::to_string(dense.size()) +
@@ -634,15 +674,16 @@ PYBIND11_MODULE(_hipstore, m) {
                                 bool overwrite,
                                 std::optional<std::string> base_map,
                                 std::optional<std::string> map_out,
-                                bool compress) {
+                                bool compress, std::optional<py::bytes> key) {
     DeltaInfo info;
     DeltaMaps maps;
+    const KeyArg key_arg(key);
     maps.base_map = base_map.value_or("");
     maps.map_out = map_out.value_or("");
     delta_call("bdev_export_delta", [&](std::string* error) {
       return bdev_export_delta(src.get(), base ? base->get() : nullptr, path,
                                granule.value_or(0), overwrite, &maps, &info,
-                               error, compress);
+                               error, compress, key_arg.ptr());
     });
     py::dict d = delta_info_to_dict(info);
     if (!maps.map_out.empty()) d["map_bytes"] = maps.map_bytes;
@@ -650,12 +691,121 @@ PYBIND11_MODULE(_hipstore, m) {
   }, py::arg("src"), py::arg("path"), py::arg("base") = py::none(),
      py::arg("granule") = py::none(), py::arg("overwrite") = false,
      py::arg("base_map") = py::none(), py::arg("map_out") = py::none(),
-     py::arg("compress") = false,
+     py::arg("compress") = false, py::arg("key") = py::none(),
      "Write the granules of src that differ from base, or from the state "
      "recorded in the fingerprint map base_map (every granule without "
      "either), to a hipstore delta file; map_out also writes the "
      "fingerprint map of src; compress writes a version-2 file of HSLZ1 "
-     "pieces");
+     "pieces, key (64 bytes) a version-3 file of HSXTS1 ciphertext");
+
+  m.def("xts_encrypt_units", [](py::bytes data, uint32_t granule,
+                                py::bytes key, uint64_t first_unit) {
+    const std::string in = data;
+    const std::string raw_key = key;
+    check_units("xts_encrypt_units", in, granule, raw_key);
+    const XtsSchedules keys(reinterpret_cast<const uint8_t*>(raw_key.data()));
+    std::string out(in.size(), '\0');
+    for (uint64_t i = 0; i < in.size() / granule; ++i) {
+      xts_encrypt_unit(keys, first_unit + i,
+                       reinterpret_cast<const uint8_t*>(in.data()) + i * granule,
+                       reinterpret_cast<uint8_t*>(&out[0]) + i * granule,
+                       granule);
+    }
+    return py::bytes(out);
+  }, py::arg("data"), py::arg("granule"), py::arg("key"),
+     py::arg("first_unit") = 0,
+     "HSXTS1 (AES-256-XTS) over whole granules, data unit i numbered "
+     "first_unit + i (host codec, the byte model of k_xts_pack_marked)");
+
+  m.def("xts_decrypt_units", [](py::bytes data, uint32_t granule,
+                                py::bytes key, uint64_t first_unit) {
+    const std::string in = data;
+    const std::string raw_key = key;
+    check_units("xts_decrypt_units", in, granule, raw_key);
+    const XtsSchedules keys(reinterpret_cast<const uint8_t*>(raw_key.data()));
+    std::string out(in.size(), '\0');
+    for (uint64_t i = 0; i < in.size() / granule; ++i) {
+      xts_decrypt_unit(keys, first_unit + i,
+                       reinterpret_cast<const uint8_t*>(in.data()) + i * granule,
+                       reinterpret_cast<uint8_t*>(&out[0]) + i * granule,
+                       granule);
+    }
+    return py::bytes(out);
+  }, py::arg("data"), py::arg("granule"), py::arg("key"),
+     py::arg("first_unit") = 0, "The inverse of xts_encrypt_units (host codec)");
+
+  m.def("xts_kcv", [](py::bytes key) {
+    const std::string raw_key = key;
+    check_units("xts_kcv", "", 16, raw_key);
+    return xts_kcv(reinterpret_cast<const uint8_t*>(raw_key.data()));
+  }, py::arg("key"),
+     "Key check value of an HSXTS1 key, as in a version-3 delta header");
+
+  m.def("bdev_xts_pack_marked", [](BdevPtr src, py::bytes bitmap,
+                                   uint32_t granule, py::bytes key,
+                                   uint64_t first_unit, uint64_t src_offset,
+                                   std::optional<uint64_t> length,
+                                   uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len = marked_range("bdev_xts_pack_marked", *src, src_offset,
+                                      length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    const KeyArg key_arg(key);
+    std::string out;
+    delta_call("bdev_xts_pack_marked", [&](std::string* error) {
+      *error = "bad key, granule, range or first_unit, or the pack failed";
+      return bdev_xts_pack_marked_sync(
+          src.get(), src_offset, len, granule, words, key_arg.bytes.data(),
+          key_arg.bytes.size(), first_unit, staging_bytes,
+          [&out, granule](const uint8_t* data, uint64_t, uint64_t count) {
+            out.append(reinterpret_cast<const char*>(data), count * granule);
+            return 0;
+          });
+    });
+    return py::bytes(out);
+  }, py::arg("src"), py::arg("bitmap"), py::arg("granule"), py::arg("key"),
+     py::arg("first_unit") = 0, py::arg("src_offset") = 0,
+     py::arg("length") = py::none(), py::arg("staging_bytes") = 0,
+     "bdev_pack_marked with every granule HSXTS1-encrypted as data unit "
+     "first_unit + its index in the range (k_xts_pack_marked for HBM bdevs)");
+
+  m.def("bdev_xts_unpack_marked", [](BdevPtr dst, py::bytes bitmap,
+                                     uint32_t granule, py::bytes data,
+                                     py::bytes key, uint64_t first_unit,
+                                     uint64_t dst_offset,
+                                     std::optional<uint64_t> length,
+                                     uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len = marked_range("bdev_xts_unpack_marked", *dst,
+                                      dst_offset, length, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    const std::string dense = data;
+    if (granule != 0 &&
+        dense.size() != marks_below(words, len / granule) * granule) {
+      throw std::invalid_argument(
+          "bdev_xts_unpack_marked: data length is not marked * granule");
+    }
+    const KeyArg key_arg(key);
+    uint64_t unpacked = 0;
+    delta_call("bdev_xts_unpack_marked", [&](std::string* error) {
+      *error = "bad key, granule, range or first_unit, or the unpack failed";
+      return bdev_xts_unpack_marked_sync(
+          dst.get(), dst_offset, len, granule, words, key_arg.bytes.data(),
+          key_arg.bytes.size(), first_unit, staging_bytes,
+          [&dense, granule](uint8_t* out, uint64_t first_rank,
+                            uint64_t count) {
+            memcpy(out, dense.data() + first_rank * granule, count * granule);
+            return 0;
+          },
+          &unpacked);
+    });
+    return unpacked;
+  }, py::arg("dst"), py::arg("bitmap"), py::arg("granule"), py::arg("data"),
+     py::arg("key"), py::arg("first_unit") = 0, py::arg("dst_offset") = 0,
+     py::arg("length") = py::none(), py::arg("staging_bytes") = 0,
+     "Decrypt the ciphertext of bdev_xts_pack_marked into the granules "
+     "marked in `bitmap` (k_xts_unpack_marked for HBM bdevs); returns the "
+     "number written");
 
   m.def("lz_compress_granule", [](py::bytes data) {
     const std::string in = data;
@@ -772,16 +922,59 @@ PYBIND11_MODULE(_hipstore, m) {
      "`bitmap`; every piece is validated on the host first. Returns the "
      "number written");
 
+  m.def("xts_marked_probe", [](BdevPtr bdev, py::bytes bitmap,
+                               uint32_t granule, py::bytes key, bool unpack,
+                               uint64_t staging_bytes) {
+    const std::string raw = bitmap;
+    const uint64_t len =
+        marked_range("xts_marked_probe", *bdev, 0, std::nullopt, granule, raw);
+    const std::vector<uint64_t> words = bitmap_words(raw);
+    const KeyArg key_arg(key);
+    uint64_t moved = 0;
+    double seconds = 0;
+    delta_call("xts_marked_probe", [&](std::string* error) {
+      *error = "bad key, granule or range, or the call failed";
+      const auto t0 = std::chrono::steady_clock::now();
+      const int status =
+          unpack ? bdev_xts_unpack_marked_sync(
+                       bdev.get(), 0, len, granule, words,
+                       key_arg.bytes.data(), key_arg.bytes.size(), 0,
+                       staging_bytes,
+                       [](uint8_t*, uint64_t, uint64_t) { return 0; }, &moved)
+                 : bdev_xts_pack_marked_sync(
+                       bdev.get(), 0, len, granule, words,
+                       key_arg.bytes.data(), key_arg.bytes.size(), 0,
+                       staging_bytes,
+                       [](const uint8_t*, uint64_t, uint64_t) { return 0; },
+                       &moved);
+      seconds = std::chrono::duration<double>(
+                    std::chrono::steady_clock::now() - t0).count();
+      return status;
+    });
+    py::dict d;
+    d["seconds"] = seconds;
+    d["granules"] = moved;
+    return d;
+  }, py::arg("bdev"), py::arg("bitmap"), py::arg("granule"), py::arg("key"),
+     py::arg("unpack") = false, py::arg("staging_bytes") = 0,
+     "Measurement aid (tools/crypt_bench.py): bdev_xts_pack_marked with a "
+     "discarding sink, or with unpack bdev_xts_unpack_marked with a source "
+     "that leaves the staging buffer as it is (the volume is overwritten)");
+
   m.def("bdev_import_delta", [](BdevPtr dst, const std::string& path,
-                                bool dry_run) {
+                                bool dry_run, std::optional<py::bytes> key) {
     DeltaInfo info;
+    const KeyArg key_arg(key);
     delta_call("bdev_import_delta", [&](std::string* error) {
-      return bdev_import_delta(dst.get(), path, dry_run, &info, error);
+      return bdev_import_delta(dst.get(), path, dry_run, &info, error,
+                               key_arg.ptr());
     });
     return delta_info_to_dict(info);
   }, py::arg("dst"), py::arg("path"), py::arg("dry_run") = false,
+     py::arg("key") = py::none(),
      "Apply a hipstore delta file to dst; dry_run checks everything and "
-     "writes nothing");
+     "writes nothing. A version-3 file needs its key (dry_run works "
+     "without one)");
 
   m.def("delta_file_info", [](const std::string& path) {
     DeltaInfo info;

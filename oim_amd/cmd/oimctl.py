@@ -86,6 +86,11 @@ def main(argv=None) -> int:
             cmd.add_argument("--compress", action="store_true",
                              help="store every granule LZ-compressed "
                              "(restore reads either kind of file)")
+        if name in ("checkpoint", "restore"):
+            cmd.add_argument("--key-file", default="",
+                             help="file of 64 raw bytes on the data-path "
+                             "daemon's host: AES-256-XTS key of an "
+                             "encrypted checkpoint")
         if name == "restore":
             cmd.add_argument("--dry-run", action="store_true",
                              help="check the file, write nothing")
@@ -171,7 +176,7 @@ def main(argv=None) -> int:
                         bdev_name=args.volume, base_name=args.base,
                         path=args.path, overwrite=args.overwrite,
                         base_map=args.base_map, map_out=args.map_out,
-                        compress=args.compress),
+                        compress=args.compress, key_file=args.key_file),
                     metadata=metadata, timeout=600)
                 print(f"checkpointed {args.volume} -> {args.path}: "
                       f"{reply.saved} of {reply.granules} granules, "
@@ -180,7 +185,7 @@ def main(argv=None) -> int:
                 reply = controller.RestoreMallocBDev(
                     spec.RestoreMallocBDevRequest(
                         bdev_name=args.volume, path=args.path,
-                        dry_run=args.dry_run),
+                        dry_run=args.dry_run, key_file=args.key_file),
                     metadata=metadata, timeout=600)
                 verb = "verified" if args.dry_run else "restored"
                 print(f"{verb} {args.volume} <- {args.path}: "

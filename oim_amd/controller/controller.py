@@ -418,7 +418,8 @@ class Controller(spec.ControllerServicer):
                         overwrite=request.overwrite,
                         base_map=request.base_map or None,
                         map_out=request.map_out or None,
-                        compress=request.compress)
+                        compress=request.compress,
+                        key_file=request.key_file or None)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.CheckpointMallocBDevReply(
@@ -437,7 +438,8 @@ class Controller(spec.ControllerServicer):
                 self._require_bdev(client, name, context)
                 try:
                     result = hipstore.bdev_import_delta(
-                        client, name, path, dry_run=request.dry_run)
+                        client, name, path, dry_run=request.dry_run,
+                        key_file=request.key_file or None)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.RestoreMallocBDevReply(granules=result["granules"],

@@ -338,7 +338,8 @@ def bdev_export_delta(client: Client, name: str, path: str,
                       overwrite: bool = False,
                       base_map: Optional[str] = None,
                       map_out: Optional[str] = None,
-                      compress: bool = False) -> Dict:
+                      compress: bool = False,
+                      key_file: Optional[str] = None) -> Dict:
     """Checkpoint a volume to a delta file: every granule, or with
     `base` (an earlier clone) or `base_map` (the fingerprint map written
     with an earlier checkpoint; no clone needed) only the granules that
@@ -346,6 +347,9 @@ def bdev_export_delta(client: Client, name: str, path: str,
     fingerprint map, the base_map of the next checkpoint. `compress`
     stores every granule LZ-compressed (a version-2 file; granules of
     512 to 16384 bytes); bdev_import_delta reads either version.
+    `key_file` names a file of exactly 64 raw bytes that the daemon
+    reads: every granule is stored AES-256-XTS encrypted (a version-3
+    file; not together with compress). The key itself never travels.
 
     Returns {granule, granules, saved, file_bytes, full}, with map_out
     also map_bytes and with compress stored_bytes (the bytes the granules
@@ -364,18 +368,25 @@ def bdev_export_delta(client: Client, name: str, path: str,
         params["overwrite"] = True
     if compress:
         params["compress"] = True
+    if key_file is not None:
+        params["key_file"] = key_file
     return client.invoke("bdev_export_delta", params)
 
 
 def bdev_import_delta(client: Client, name: str, path: str,
-                      dry_run: bool = False) -> Dict:
+                      dry_run: bool = False,
+                      key_file: Optional[str] = None) -> Dict:
     """Apply a delta file to an unclaimed volume; dry_run checks the
-    file (every CRC) and writes nothing.
+    file (every CRC) and writes nothing. An encrypted (version-3) file
+    needs the `key_file` it was written with; a wrong key is refused
+    before anything is written, and dry_run works without a key.
 
     Returns {granule, granules, applied}."""
     params: Dict = {"name": name, "path": path}
     if dry_run:
         params["dry_run"] = True
+    if key_file is not None:
+        params["key_file"] = key_file
     return client.invoke("bdev_import_delta", params)
 
 

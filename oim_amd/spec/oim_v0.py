@@ -75,13 +75,13 @@ MESSAGES = [
             [Field("bdev_name", 1, "string"), Field("base_name", 2, "string"),
              Field("path", 3, "string"), Field("overwrite", 4, "bool"),
              Field("base_map", 5, "string"), Field("map_out", 6, "string"),
-             Field("compress", 7, "bool")]),
+             Field("compress", 7, "bool"), Field("key_file", 8, "string")]),
     Message("CheckpointMallocBDevReply",
             [Field("granules", 1, "int64"), Field("saved", 2, "int64"),
              Field("file_bytes", 3, "int64")]),
     Message("RestoreMallocBDevRequest",
             [Field("bdev_name", 1, "string"), Field("path", 2, "string"),
-             Field("dry_run", 3, "bool")]),
+             Field("dry_run", 3, "bool"), Field("key_file", 4, "string")]),
     Message("RestoreMallocBDevReply",
             [Field("granules", 1, "int64"), Field("applied", 2, "int64")]),
     Message("VerifyMallocBDevRequest",
