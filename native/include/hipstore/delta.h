@@ -140,9 +140,33 @@ int delta_file_info(const std::string& path, DeltaInfo* info,
 // header CRC, zero reserved fields, consistent geometry, exact file
 // length, trailer); every record's CRC is then checked before its bytes
 // are used.
+//
+// "hipstore fingerprint map, version 2" holds HSFP2 fingerprints
+// (fingerprint.h: BLAKE2s, 16 bytes each) and is what a call with
+// map_algorithm "blake2s" writes; without it every map is version 1, byte
+// for byte as above. Same magics, same layout; it differs in the header:
+//   - version = 2 and algorithm = 2 (unkeyed) or 3 (keyed); version 2
+//     implies one of these and they imply version 2
+//   - algorithm 3: the first reserved u32 (header bytes 40-43) is
+//     blake2s_kcv(key); every other reserved byte stays 0
+// A keyed map is a MAC over the volume: whoever rewrites a delta file or
+// the volume cannot write a map that matches without the key. The record
+// CRCs and the structural pass need no key.
 
 constexpr uint32_t kFingerprintMapVersion = 1;
+constexpr uint32_t kFingerprintMapVersionBlake2s = 2;
 constexpr uint64_t kFingerprintMapRecord = 65536;  // fingerprints per record
+
+// What a caller says about the fingerprints of the maps of a call.
+// `algorithm` 0 leaves it open: HSFP1 for a new map, whatever an existing
+// map holds otherwise. kMapBlake2s with a key is algorithm id 3, without
+// one id 2. The key is 32 bytes (kBlake2sKeyBytes).
+constexpr uint32_t kMapHsfp1 = 1;
+constexpr uint32_t kMapBlake2s = 2;
+struct MapKind {
+  uint32_t algorithm = 0;
+  const std::vector<uint8_t>* key = nullptr;
+};
 
 struct FingerprintMapInfo {
   uint32_t version = 0;
@@ -152,14 +176,17 @@ struct FingerprintMapInfo {
   uint64_t volume_bytes = 0;
   uint64_t n_granules = 0;
   uint64_t file_bytes = 0;
+  bool keyed = false;  // algorithm 3
 };
 
 // Writes the fingerprint map of the whole of `bdev` to `path` (tmp file,
 // sync, rename; an existing file is refused without `overwrite`).
-// granule 0 = the block size.
+// granule 0 = the block size. `kind`: a key of another length than 32, or
+// a key without kMapBlake2s, is kIoInvalid before the volume is read.
 int bdev_fingerprint_file(Bdev* bdev, const std::string& path,
                           uint32_t granule, bool overwrite,
-                          FingerprintMapInfo* stats, std::string* error);
+                          FingerprintMapInfo* stats, std::string* error,
+                          const MapKind& kind = MapKind());
 
 // Header fields of a map after the structural pass and every record CRC.
 int fingerprint_map_info(const std::string& path, FingerprintMapInfo* info,
@@ -176,9 +203,13 @@ struct FingerprintVerify {
   // First max_report mismatching granule indices, ascending.
   std::vector<uint64_t> first_mismatches;
 };
+// The map decides the algorithm: a `kind` that names the other one, a
+// keyed map without a key, a key for an unkeyed map and a key whose kcv
+// differs from the header's are kIoInvalid before the volume is read.
 int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
                              uint32_t max_report, FingerprintVerify* stats,
-                             std::string* error);
+                             std::string* error,
+                             const MapKind& kind = MapKind());
 
 // bdev_export_delta with fingerprint maps. `base_map` names the map of
 // the base state and replaces `base` (giving both is kIoInvalid): one
@@ -205,10 +236,17 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
 // `key` writes a version-3 file (granule <= 2^24; a key of another
 // length, with equal halves, or together with `compress` is kIoInvalid).
 // `base`, `base_map` and `map_out` work unchanged with it.
+//
+// `kind` says which fingerprints the maps hold. With `base_map`, the pass
+// and `map_out` take the base map's algorithm and the rules of
+// bdev_verify_fingerprints apply; without, `map_out` is written as `kind`
+// says (default HSFP1, version 1). A kind without either map is
+// kIoInvalid. All of this is settled before anything is written.
 struct DeltaMaps {
   std::string base_map;
   std::string map_out;
   uint64_t map_bytes = 0;  // out: size of the file written to map_out
+  MapKind kind;
 };
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,

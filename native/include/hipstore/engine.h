@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "hipstore/bdev.h"
+#include "hipstore/fingerprint.h"
 
 namespace hipstore {
 
@@ -186,13 +187,21 @@ int bdev_unpack_marked_sync(Bdev* dst, uint64_t dst_offset, uint64_t length,
 // Validation is that of bdev_diff_sync on the one bdev; also kIoInvalid
 // when 0 < staging_bytes < 32 or the sink is empty. `done` receives the
 // granules delivered.
+//
+// `kind` selects the fingerprint (fingerprint.h; default HSFP1). HSFP2
+// runs hipstore::k_blake2s_granules (blake2s_ops.hip) in the same windows
+// on the GPU path and Blake2sGranuleHasher on the other. A kind that is
+// not fingerprint_kind_ok (a key that is not 32 bytes, a key with
+// algorithm 1 or 2, algorithm 3 without one) is kIoInvalid before any
+// launch.
 using FingerprintSink = std::function<int(const uint8_t* fps,
                                           uint64_t first_granule,
                                           uint64_t count)>;
 int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
                           uint32_t granule, uint64_t staging_bytes,
                           const FingerprintSink& sink,
-                          uint64_t* done = nullptr);
+                          uint64_t* done = nullptr,
+                          const FingerprintKind& kind = FingerprintKind());
 
 // Measurement aid for tools/delta_bench.py: moves the marked bytes of
 // an HBM bdev to pinned host memory by plain hipMemcpyAsync (mode 0: one

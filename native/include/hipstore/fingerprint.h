@@ -17,15 +17,38 @@
 //   without a vector); the fingerprint is F0 then F1, 8 LE bytes each.
 // A changed granule is missed with probability about 2^-64. The hash is
 // not cryptographic: whoever controls the data can construct collisions.
+// HSFP2 below is the choice where that matters.
+//
+// "HSFP2" (algorithm ids 2 and 3): BLAKE2s (RFC 7693, sequential mode)
+// with a 16-byte digest per granule,
+//   fp(granule) = blake2s(granule, digest_size = 16, key = K,
+//                         person = "HSFP2\0\0\0")
+// fanout 1, depth 1, no salt. K is empty for algorithm 2 (a
+// collision-resistant drop-in for HSFP1: 64-bit collision resistance) and
+// kBlake2sKeyBytes = 32 bytes for algorithm 3 (BLAKE2s' own keyed mode, a
+// MAC: a map cannot be forged without K). G % 16 == 0 as above; the
+// fingerprint depends on the granule's bytes and on K only. The key check
+// value of a keyed map is the first four bytes, little-endian, of
+//   blake2s("", digest_size = 16, key = K, person = "HSFP2kcv").
+// The chaining value after the parameter block (and, keyed, after the key
+// block) is the same for every granule: blake2s_granule_midstate computes
+// it once per call, and it is all hipstore::k_blake2s_granules
+// (blake2s_ops.hip) and Blake2sGranuleHasher start from. It is
+// key-equivalent: clear copies of it like a key.
 
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 namespace hipstore {
 
 constexpr uint32_t kFingerprintBytes = 16;
 constexpr uint32_t kFingerprintAlgorithm = 1;
+constexpr uint32_t kFingerprintBlake2s = 2;
+constexpr uint32_t kFingerprintBlake2sKeyed = 3;
+constexpr uint32_t kBlake2sKeyBytes = 32;
+constexpr uint32_t kBlake2sBlockBytes = 64;
 constexpr uint32_t kFingerprintStreams = 64;
 
 constexpr uint64_t kFingerprintP1 = 0x9E3779B185EBCA87ull;
@@ -53,5 +76,70 @@ class GranuleHasher {
 // (granule % 16 == 0) into out[0 .. n * 16).
 void fingerprint_granules(const void* data, uint64_t n, uint32_t granule,
                           uint8_t* out);
+
+// Which fingerprint a call computes: the algorithm id and, for id 3 only,
+// the key. The default is HSFP1.
+struct FingerprintKind {
+  uint32_t algorithm = kFingerprintAlgorithm;
+  const uint8_t* key = nullptr;
+  size_t key_bytes = 0;
+};
+
+// Algorithm 1 or 2 without a key, or 3 with a key of 32 bytes.
+bool fingerprint_kind_ok(const FingerprintKind& kind);
+
+// Where every HSFP2 granule starts: h after the parameter block and, when
+// keyed, the key block; t0 is 0 or 64.
+struct Blake2sMidstate {
+  uint32_t h[8];
+  uint32_t t0;
+};
+
+// Plain scalar BLAKE2s straight from RFC 7693: out_bytes 1..32, key of
+// 0..32 bytes, an optional 8-byte personalisation. update() takes any
+// length; the last block is held back until finish(), which may be called
+// once.
+class Blake2s {
+ public:
+  Blake2s(uint32_t out_bytes, const uint8_t* key, size_t key_bytes,
+          const uint8_t* person8 = nullptr);
+  // Continues from a chaining value reached after start.t0 bytes.
+  Blake2s(uint32_t out_bytes, const Blake2sMidstate& start);
+  ~Blake2s();
+  void update(const void* data, uint64_t len);
+  void finish(uint8_t* out);
+
+ private:
+  uint32_t h_[8];
+  uint64_t t_ = 0;
+  uint8_t buf_[kBlake2sBlockBytes];
+  uint32_t fill_ = 0;
+  uint32_t out_bytes_;
+};
+
+// `kind` must be fingerprint_kind_ok with algorithm 2 or 3.
+void blake2s_granule_midstate(const FingerprintKind& kind,
+                              Blake2sMidstate* out);
+
+// The key check value of a keyed map.
+uint32_t blake2s_kcv(const uint8_t key[kBlake2sKeyBytes]);
+
+// GranuleHasher's contract for HSFP2.
+class Blake2sGranuleHasher {
+ public:
+  explicit Blake2sGranuleHasher(const Blake2sMidstate& start);
+  ~Blake2sGranuleHasher();
+  void update(const void* data, uint64_t len) { cur_.update(data, len); }
+  void finish(uint8_t out[kFingerprintBytes]);
+
+ private:
+  Blake2sMidstate start_;
+  Blake2s cur_;
+};
+
+// fingerprint_granules for any algorithm; false when `kind` is not
+// fingerprint_kind_ok.
+bool fingerprint_granules(const void* data, uint64_t n, uint32_t granule,
+                          const FingerprintKind& kind, uint8_t* out);
 
 }  // namespace hipstore

@@ -16,6 +16,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "blake2s_internal.h"
 #include "gpu_internal.h"
 #include "marked_internal.h"
 #include "hipstore/crc32c.h"
@@ -979,10 +980,12 @@ uint32_t fingerprint_grid(uint64_t n_granules) {
 
 // One launch per window of `window` granules, fingerprints written in
 // place into one half of `prints`; window k+1 runs while the sink sees
-// window k.
+// window k. `start` is null for HSFP1 and the midstate of the call for
+// HSFP2.
 int fingerprint_gpu(int device, Bdev* bdev, uint64_t offset,
                     uint64_t n_granules, uint32_t granule, uint64_t window,
-                    const FingerprintSink& sink, uint64_t* done) {
+                    const Blake2sMidstate* start, const FingerprintSink& sink,
+                    uint64_t* done) {
   HalvesStream hs(device);
   const uint64_t half_bytes = window * kFingerprintBytes;
   uint8_t* prints = bulk_ctx().prints.reserve(2 * half_bytes);
@@ -990,10 +993,15 @@ int fingerprint_gpu(int device, Bdev* bdev, uint64_t offset,
   const uint8_t* base = static_cast<uint8_t*>(bdev->device_base()) + offset;
   auto launch = [&](uint64_t first, int half) {
     const uint64_t count = std::min(window, n_granules - first);  // >= 1
-    hipLaunchKernelGGL(k_fingerprint_granules, dim3(fingerprint_grid(count)),
-                       dim3(kWavesPerWg * 64), 0, hs.stream,
-                       base + first * granule, count, granule,
-                       reinterpret_cast<uint4*>(dev_prints + half * half_bytes));
+    if (start != nullptr) {
+      launch_blake2s_granules(hs.stream, base + first * granule, count,
+                              granule, *start, dev_prints + half * half_bytes);
+    } else {
+      hipLaunchKernelGGL(
+          k_fingerprint_granules, dim3(fingerprint_grid(count)),
+          dim3(kWavesPerWg * 64), 0, hs.stream, base + first * granule, count,
+          granule, reinterpret_cast<uint4*>(dev_prints + half * half_bytes));
+    }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(hs.done[half], hs.stream));
   };
@@ -1011,9 +1019,11 @@ int fingerprint_gpu(int device, Bdev* bdev, uint64_t offset,
 }
 
 // Generic path: the same windows, read in spans of at most 1 MiB through
-// the incremental hasher (a granule may be larger than a span).
+// the incremental hasher (a granule may be larger than a span): a
+// GranuleHasher or a Blake2sGranuleHasher.
+template <typename Hasher>
 int fingerprint_generic(Bdev* bdev, uint64_t offset, uint64_t n_granules,
-                        uint32_t granule, uint64_t window,
+                        uint32_t granule, uint64_t window, Hasher& hasher,
                         const FingerprintSink& sink, uint64_t* done) {
   // Spans are cut on multiples of the block size and of 16.
   const uint64_t unit = std::lcm<uint64_t>(bdev->block_size(), 16);
@@ -1021,7 +1031,6 @@ int fingerprint_generic(Bdev* bdev, uint64_t offset, uint64_t n_granules,
   if (span == 0) return kIoInvalid;
   uint8_t* prints = bulk_ctx().prints.reserve(window * kFingerprintBytes);
   uint8_t* buf = bulk_ctx().chunks.reserve(2 * kDiffHostChunk);
-  GranuleHasher hasher;
   while (*done < n_granules) {
     const uint64_t first = *done;
     const uint64_t count = std::min(window, n_granules - first);
@@ -1056,16 +1065,24 @@ int fingerprint_generic(Bdev* bdev, uint64_t offset, uint64_t n_granules,
 
 int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
                           uint32_t granule, uint64_t staging_bytes,
-                          const FingerprintSink& sink, uint64_t* done_out) {
+                          const FingerprintSink& sink, uint64_t* done_out,
+                          const FingerprintKind& kind) {
   uint64_t unused = 0;
   uint64_t* done = done_out != nullptr ? done_out : &unused;
   *done = 0;
+  // The midstate is key-equivalent: cleared on every way out.
+  struct Start {
+    Blake2sMidstate mid;
+    ~Start() { explicit_bzero(&mid, sizeof(mid)); }
+  } start;
   try {
     if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule) ||
         (staging_bytes != 0 && staging_bytes < 2 * kFingerprintBytes) ||
-        !sink) {
+        !sink || !fingerprint_kind_ok(kind)) {
       return kIoInvalid;
     }
+    const bool blake = kind.algorithm != kFingerprintAlgorithm;
+    if (blake) blake2s_granule_midstate(kind, &start.mid);
     const uint64_t n_granules = length / granule;  // >= 1
     const uint64_t half =
         staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
@@ -1074,10 +1091,16 @@ int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
     const int device = granule_kernel_device(bdev, bdev);
     if (device >= 0) {
       return fingerprint_gpu(device, bdev, offset, n_granules, granule, window,
-                             sink, done);
+                             blake ? &start.mid : nullptr, sink, done);
     }
-    return fingerprint_generic(bdev, offset, n_granules, granule, window, sink,
-                               done);
+    if (blake) {
+      Blake2sGranuleHasher hasher(start.mid);
+      return fingerprint_generic(bdev, offset, n_granules, granule, window,
+                                 hasher, sink, done);
+    }
+    GranuleHasher hasher;
+    return fingerprint_generic(bdev, offset, n_granules, granule, window,
+                               hasher, sink, done);
   } catch (const std::exception&) {
     return kIoFailed;
   }

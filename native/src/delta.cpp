@@ -38,6 +38,9 @@ const Format kDeltaXts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
 const Format kMap = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
                      {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
                      kFingerprintMapVersion, "fingerprint map"};
+const Format kMapBlake2s2 = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
+                             {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
+                             kFingerprintMapVersionBlake2s, "fingerprint map"};
 
 const char kBadGranule[] =
     "invalid granule (a multiple of the block size and of 16 that divides "
@@ -268,27 +271,90 @@ int write_delta(OutFile* out, Bdev* src, const std::vector<uint64_t>& bitmap,
 struct LoadedMap {
   FingerprintMapInfo info;
   std::vector<uint8_t> fps;  // n_granules * 16 bytes
+  uint32_t kcv = 0;          // algorithm 3
 };
+
+// The fingerprint of a call's maps, settled: the kind points into the
+// caller's key.
+struct MapChoice {
+  FingerprintKind kind;
+  uint32_t kcv = 0;
+};
+
+// For a map that the call writes from nothing.
+int choose_new(const MapKind& want, MapChoice* out, std::string* error) {
+  if (want.algorithm > kMapBlake2s) {
+    return fail(error, kIoInvalid, "unknown map_algorithm");
+  }
+  if (want.key != nullptr && want.algorithm != kMapBlake2s) {
+    return fail(error, kIoInvalid, "map_key needs map_algorithm blake2s");
+  }
+  if (want.key != nullptr && want.key->size() != kBlake2sKeyBytes) {
+    return fail(error, kIoInvalid, "the map key must be 32 bytes");
+  }
+  *out = MapChoice();
+  if (want.algorithm == kMapBlake2s) {
+    out->kind.algorithm = kFingerprintBlake2s;
+    if (want.key != nullptr) {
+      out->kind = {kFingerprintBlake2sKeyed, want.key->data(),
+                   want.key->size()};
+      out->kcv = blake2s_kcv(want.key->data());
+    }
+  }
+  return kIoOk;
+}
+
+// For a pass against the map `stored`, which decides the algorithm.
+int choose_stored(const MapKind& want, const LoadedMap& stored,
+                  MapChoice* out, std::string* error) {
+  const uint32_t family =
+      stored.info.algorithm == kFingerprintAlgorithm ? kMapHsfp1 : kMapBlake2s;
+  if (want.algorithm != 0 && want.algorithm != family) {
+    return fail(error, kIoInvalid, "map_algorithm differs from the map's");
+  }
+  if (want.key != nullptr && !stored.info.keyed) {
+    return fail(error, kIoInvalid, "a map key was given for an unkeyed map");
+  }
+  if (want.key == nullptr && stored.info.keyed) {
+    return fail(error, kIoInvalid, "the map is keyed: a map key is required");
+  }
+  MapKind same = want;
+  same.algorithm = family;
+  const int status = choose_new(same, out, error);
+  if (status != kIoOk) return status;
+  if (stored.info.keyed && out->kcv != stored.kcv) {
+    return fail(error, kIoInvalid,
+                "wrong map key (key check value differs from the map's)");
+  }
+  return kIoOk;
+}
 
 // Structural pass, then every record with its CRC checked before its
 // bytes are kept.
 int load_map(const std::string& path, LoadedMap* out, std::string* error) {
   InFile in;
-  int status = in.open(path, kMap, error);
+  int status = in.open(path, kMap, error, &kMapBlake2s2);
   if (status != kIoOk) return status;
   const Header& h = in.header;
   FingerprintMapInfo& info = out->info;
-  info.version = kFingerprintMapVersion;
+  info.version = in.format().version;
   info.block_size = h.block_size;
   info.granule = h.granule;
   info.algorithm = h.word;
   info.volume_bytes = h.volume_bytes;
   info.n_granules = h.n_granules;
   info.file_bytes = in.file_bytes;
-  if (info.algorithm != kFingerprintAlgorithm) {
+  // Version 1 holds algorithm 1, version 2 algorithm 2 or 3.
+  const bool blake = info.algorithm == kFingerprintBlake2s ||
+                     info.algorithm == kFingerprintBlake2sKeyed;
+  if (info.version == kFingerprintMapVersion
+          ? info.algorithm != kFingerprintAlgorithm
+          : !blake) {
     return fail(error, kIoInvalid, "unknown fingerprint algorithm");
   }
-  if (std::any_of(h.owned, h.owned + sizeof(h.owned),
+  info.keyed = info.algorithm == kFingerprintBlake2sKeyed;
+  if (info.keyed) out->kcv = get_u32(h.owned);
+  if (std::any_of(h.owned + (info.keyed ? 4 : 0), h.owned + sizeof(h.owned),
                   [](uint8_t b) { return b != 0; })) {
     return fail(error, kIoInvalid, "non-zero reserved field");
   }
@@ -311,16 +377,21 @@ int load_map(const std::string& path, LoadedMap* out, std::string* error) {
 // fingerprints are `fps`. Fills *info.
 int write_map(OutFile* out, uint64_t block_size, uint32_t granule,
               uint64_t length, const std::vector<uint8_t>& fps,
-              FingerprintMapInfo* info, std::string* error) {
-  info->version = kFingerprintMapVersion;
+              const MapChoice& choice, FingerprintMapInfo* info,
+              std::string* error) {
+  const bool blake = choice.kind.algorithm != kFingerprintAlgorithm;
+  info->version =
+      blake ? kFingerprintMapVersionBlake2s : kFingerprintMapVersion;
   info->block_size = static_cast<uint32_t>(block_size);
   info->granule = granule;
-  info->algorithm = kFingerprintAlgorithm;
+  info->algorithm = choice.kind.algorithm;
+  info->keyed = choice.kind.algorithm == kFingerprintBlake2sKeyed;
   info->volume_bytes = length;
   info->n_granules = fps.size() / kFingerprintBytes;
-  const Header h = {info->block_size, granule, kFingerprintAlgorithm, length,
-                    info->n_granules, {0}};
-  int status = out->begin(kMap, h, error);
+  Header h = {info->block_size, granule, info->algorithm, length,
+              info->n_granules, {0}};
+  if (info->keyed) put_u32(h.owned, choice.kcv);
+  int status = out->begin(blake ? kMapBlake2s2 : kMap, h, error);
   if (status != kIoOk) return status;
   RecordWriter writer(out, kFingerprintBytes, kFingerprintMapRecord,
                       info->n_granules);
@@ -334,6 +405,7 @@ int write_map(OutFile* out, uint64_t block_size, uint32_t granule,
 // of `bitmap` is set when granule g has no stored fingerprint or differs
 // from it; with `keep`, the fingerprints are kept.
 int fingerprint_pass(Bdev* bdev, uint64_t length, uint32_t granule,
+                     const FingerprintKind& kind,
                      const std::vector<uint8_t>* stored,
                      std::vector<uint64_t>* bitmap,
                      std::vector<uint8_t>* keep) {
@@ -365,7 +437,7 @@ int fingerprint_pass(Bdev* bdev, uint64_t length, uint32_t granule,
         }
         return 0;
       },
-      &done);
+      &done, kind);
   if (status == kIoOk && done != n_granules) return kIoFailed;
   return status;
 }
@@ -378,11 +450,14 @@ struct Marked {
   std::vector<uint8_t> fps;  // of src, where a pass kept them for map_out
 };
 
-// Against the fingerprint map `base_map`, whose granule the export takes.
-int mark_against_map(Bdev* src, const std::string& base_map, bool keep_fps,
-                     uint32_t* granule, Marked* out, std::string* error) {
+// Against the fingerprint map `base_map`, whose granule and algorithm the
+// export takes.
+int mark_against_map(Bdev* src, const std::string& base_map,
+                     const MapKind& want, bool keep_fps, uint32_t* granule,
+                     MapChoice* choice, Marked* out, std::string* error) {
   LoadedMap stored;
   int status = load_map(base_map, &stored, error);
+  if (status == kIoOk) status = choose_stored(want, stored, choice, error);
   if (status != kIoOk) return status;
   if (*granule != 0 && *granule != stored.info.granule) {
     return fail(error, kIoInvalid,
@@ -395,8 +470,9 @@ int mark_against_map(Bdev* src, const std::string& base_map, bool keep_fps,
     return fail(error, kIoInvalid,
                 "base map has another block size or a larger volume");
   }
-  status = fingerprint_pass(src, src->size_bytes(), *granule, &stored.fps,
-                            &out->bitmap, keep_fps ? &out->fps : nullptr);
+  status = fingerprint_pass(src, src->size_bytes(), *granule, choice->kind,
+                            &stored.fps, &out->bitmap,
+                            keep_fps ? &out->fps : nullptr);
   if (status == kIoInvalid) return fail(error, kIoInvalid, kBadGranule);
   if (status != kIoOk) return fail(error, kIoFailed, "fingerprint pass failed");
   out->n_marked = popcount(out->bitmap);
@@ -523,6 +599,16 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   if (map_out == path) {
     return fail(error, kIoInvalid, "map_out names the delta file");
   }
+  const MapKind want = maps != nullptr ? maps->kind : MapKind();
+  MapChoice choice;
+  if (base_map.empty()) {
+    if (map_out.empty() && (want.algorithm != 0 || want.key != nullptr)) {
+      return fail(error, kIoInvalid,
+                  "map_algorithm and map_key need base_map or map_out");
+    }
+    const int chosen = choose_new(want, &choice, error);
+    if (chosen != kIoOk) return chosen;
+  }
   if (src->block_size() > UINT32_MAX) {
     return fail(error, kIoInvalid, "block size too large");
   }
@@ -532,8 +618,8 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   Marked marked;
   int status;
   if (!base_map.empty()) {
-    status = mark_against_map(src, base_map, !map_out.empty(), &granule,
-                              &marked, error);
+    status = mark_against_map(src, base_map, want, !map_out.empty(), &granule,
+                              &choice, &marked, error);
   } else if (base != nullptr) {
     status = mark_against_clone(src, base, granule, &marked, error);
   } else {
@@ -569,8 +655,8 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   // The map is taken before the pack pass: a write in between leaves it
   // older than the exported data, never newer.
   if (!map_out.empty() && base_map.empty() &&
-      fingerprint_pass(src, info.volume_bytes, granule, nullptr, nullptr,
-                       &marked.fps) != kIoOk) {
+      fingerprint_pass(src, info.volume_bytes, granule, choice.kind, nullptr,
+                       nullptr, &marked.fps) != kIoOk) {
     return fail(error, kIoFailed, "fingerprint pass failed");
   }
   // Both files are complete under their .tmp names before either
@@ -582,7 +668,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   status = write_delta(&delta, src, marked.bitmap, key, &info, error);
   if (status == kIoOk && !map_out.empty()) {
     status = write_map(&map, src->block_size(), granule, info.volume_bytes,
-                       marked.fps, &map_info, error);
+                       marked.fps, choice, &map_info, error);
   }
   if (status == kIoOk) status = delta.publish(error);
   if (status != kIoOk) return status;
@@ -683,7 +769,8 @@ int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
 
 int bdev_fingerprint_file(Bdev* bdev, const std::string& path,
                           uint32_t granule, bool overwrite,
-                          FingerprintMapInfo* stats, std::string* error) {
+                          FingerprintMapInfo* stats, std::string* error,
+                          const MapKind& kind) {
   if (bdev == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
   }
@@ -691,17 +778,19 @@ int bdev_fingerprint_file(Bdev* bdev, const std::string& path,
     return fail(error, kIoInvalid, "block size too large");
   }
   if (granule == 0) granule = static_cast<uint32_t>(bdev->block_size());
-  int status = refuse_existing(path, overwrite, error);
+  MapChoice choice;
+  int status = choose_new(kind, &choice, error);
+  if (status == kIoOk) status = refuse_existing(path, overwrite, error);
   if (status != kIoOk) return status;
   std::vector<uint8_t> fps;
-  status = fingerprint_pass(bdev, bdev->size_bytes(), granule, nullptr,
-                            nullptr, &fps);
+  status = fingerprint_pass(bdev, bdev->size_bytes(), granule, choice.kind,
+                            nullptr, nullptr, &fps);
   if (status == kIoInvalid) return fail(error, kIoInvalid, kBadGranule);
   if (status != kIoOk) return fail(error, kIoFailed, "fingerprint pass failed");
   OutFile out(path);
   FingerprintMapInfo info;
   status = write_map(&out, bdev->block_size(), granule, bdev->size_bytes(),
-                     fps, &info, error);
+                     fps, choice, &info, error);
   if (status == kIoOk) status = out.publish(error);
   if (status == kIoOk && stats != nullptr) *stats = info;
   return status;
@@ -717,12 +806,14 @@ int fingerprint_map_info(const std::string& path, FingerprintMapInfo* info,
 
 int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
                              uint32_t max_report, FingerprintVerify* stats,
-                             std::string* error) {
+                             std::string* error, const MapKind& kind) {
   if (bdev == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
   }
   LoadedMap map;
+  MapChoice choice;
   int status = load_map(path, &map, error);
+  if (status == kIoOk) status = choose_stored(kind, map, &choice, error);
   if (status != kIoOk) return status;
   if (map.info.block_size != bdev->block_size()) {
     return fail(error, kIoInvalid,
@@ -734,7 +825,7 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
   }
   std::vector<uint64_t> bitmap;
   status = fingerprint_pass(bdev, map.info.volume_bytes, map.info.granule,
-                            &map.fps, &bitmap, nullptr);
+                            choice.kind, &map.fps, &bitmap, nullptr);
   if (status != kIoOk) {
     return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
                 "fingerprint pass failed");

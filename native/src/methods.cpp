@@ -1241,7 +1241,8 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
                     std::string(method) + ": " + why};
   };
 
-  // "key_file": a path the daemon reads, exactly 64 raw bytes (crypt.h).
+  // "key_file": a path the daemon reads, exactly 64 raw bytes (crypt.h);
+  // "map_key_file" likewise, exactly 32 (fingerprint.h, keyed HSFP2 maps).
   // Key bytes never travel in a request, a reply, a log line or
   // save_config; the copy here is cleared when the call ends.
   struct KeyFile {
@@ -1252,14 +1253,15 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
     }
     const std::vector<uint8_t>* ptr() const { return given ? &bytes : nullptr; }
   };
-  auto read_key_file = [](const Json& p, KeyFile* key) {
-    if (!p.has("key_file")) return;
-    const std::string path = p.get_string("key_file");
+  auto read_key_param = [](const Json& p, const std::string& param,
+                           size_t key_bytes, KeyFile* key) {
+    if (!p.has(param)) return;
+    const std::string path = p.get_string(param);
     const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
     if (fd < 0) {
-      throw RpcError{kInvalidParams, "key_file: cannot open " + path};
+      throw RpcError{kInvalidParams, param + ": cannot open " + path};
     }
-    key->bytes.assign(kXtsKeyBytes + 1, 0);
+    key->bytes.assign(key_bytes + 1, 0);
     size_t got = 0;
     for (ssize_t n; got < key->bytes.size() &&
                     (n = ::read(fd, key->bytes.data() + got,
@@ -1268,16 +1270,40 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
     }
     ::close(fd);
     key->given = true;
-    if (got != kXtsKeyBytes) {
+    if (got != key_bytes) {
       throw RpcError{kInvalidParams,
-                     "key_file: " + path + " must hold exactly 64 bytes"};
+                     param + ": " + path + " must hold exactly " +
+                         std::to_string(key_bytes) + " bytes"};
     }
-    key->bytes.resize(kXtsKeyBytes);
+    key->bytes.resize(key_bytes);
+  };
+  auto read_key_file = [read_key_param](const Json& p, KeyFile* key) {
+    read_key_param(p, "key_file", kXtsKeyBytes, key);
+  };
+  // "map_algorithm" ("hsfp1" / "blake2s"; absent = left open, delta.h) and
+  // "map_key_file" of the calls that read or write a fingerprint map.
+  auto map_kind_param = [read_key_param](const Json& p, KeyFile* key) {
+    MapKind kind;
+    if (p.has("map_algorithm")) {
+      const std::string algorithm = p.get_string("map_algorithm");
+      if (algorithm == "hsfp1") {
+        kind.algorithm = kMapHsfp1;
+      } else if (algorithm == "blake2s") {
+        kind.algorithm = kMapBlake2s;
+      } else {
+        throw RpcError{kInvalidParams,
+                       "map_algorithm must be \"hsfp1\" or \"blake2s\""};
+      }
+    }
+    read_key_param(p, "map_key_file", kBlake2sKeyBytes, key);
+    kind.key = key->ptr();
+    return kind;
   };
 
   server->register_method(
       "bdev_export_delta",
-      [&manager, granule_param, delta_error, read_key_file](const Json& p) {
+      [&manager, granule_param, delta_error, read_key_file,
+       map_kind_param](const Json& p) {
         // Writes a volume, or with "base" its difference from an earlier
         // clone, to a delta file (HBM volumes leave through
         // k_pack_marked, one launch per staging window; with "compress"
@@ -1306,6 +1332,8 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
                                                         : granule_param(p, src);
         KeyFile key;
         read_key_file(p, &key);
+        KeyFile map_key;
+        maps.kind = map_kind_param(p, &map_key);
         DeltaInfo info;
         std::string why;
         const int status =
@@ -1330,9 +1358,11 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
       });
 
   server->register_method(
-      "bdev_fingerprint", [&manager, granule_param, delta_error](const Json& p) {
+      "bdev_fingerprint",
+      [&manager, granule_param, delta_error, map_kind_param](const Json& p) {
         // Writes the fingerprint map of a volume (HBM volumes are hashed
-        // by k_fingerprint_granules, 16 bytes per granule leave the GPU).
+        // by k_fingerprint_granules, or k_blake2s_granules for
+        // map_algorithm "blake2s"; 16 bytes per granule leave the GPU).
         const std::string name = p.get_string("name");
         BdevPtr bdev = manager.find(name);
         if (!bdev) not_found("bdev " + name);
@@ -1340,23 +1370,29 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         if (path.empty()) throw RpcError{kInvalidParams, "path required"};
         FingerprintMapInfo info;
         std::string why;
+        KeyFile map_key;
+        const MapKind kind = map_kind_param(p, &map_key);
         const int status = bdev_fingerprint_file(
             bdev.get(), path, granule_param(p, bdev),
-            p.get_bool("overwrite", false), &info, &why);
+            p.get_bool("overwrite", false), &info, &why, kind);
         if (status != kIoOk) throw delta_error("bdev_fingerprint", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));
         o["granules"] = Json(static_cast<int64_t>(info.n_granules));
         o["map_bytes"] = Json(static_cast<int64_t>(info.file_bytes));
+        if (info.version != kFingerprintMapVersion) {
+          o["algorithm"] = Json(static_cast<int64_t>(info.algorithm));
+        }
         return Json(std::move(o));
       });
 
   server->register_method(
       "bdev_verify_fingerprints",
-      [&manager, max_report_param, indices_to_json,
-       delta_error](const Json& p) {
+      [&manager, max_report_param, indices_to_json, delta_error,
+       map_kind_param](const Json& p) {
         // Recomputes a volume's fingerprints over a map's range and
         // compares; read-only, so a claimed volume is allowed (advisory).
+        // A keyed map needs "map_key_file".
         const std::string name = p.get_string("name");
         BdevPtr bdev = manager.find(name);
         if (!bdev) not_found("bdev " + name);
@@ -1364,8 +1400,10 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         if (path.empty()) throw RpcError{kInvalidParams, "path required"};
         FingerprintVerify r;
         std::string why;
+        KeyFile map_key;
+        const MapKind kind = map_kind_param(p, &map_key);
         const int status = bdev_verify_fingerprints(
-            bdev.get(), path, max_report_param(p), &r, &why);
+            bdev.get(), path, max_report_param(p), &r, &why, kind);
         if (status != kIoOk) {
           throw delta_error("bdev_verify_fingerprints", status, why);
         }

@@ -243,7 +243,38 @@ py::dict map_info_to_dict(const FingerprintMapInfo& info) {
   d["volume_bytes"] = info.volume_bytes;
   d["granules"] = info.n_granules;
   d["file_bytes"] = info.file_bytes;
+  // version 1 keeps the keys it always had
+  if (info.version != kFingerprintMapVersion) d["keyed"] = info.keyed;
   return d;
+}
+
+// The map_algorithm / map_key arguments: None leaves the algorithm open.
+MapKind map_kind(const std::optional<std::string>& algorithm,
+                 const KeyArg& key) {
+  MapKind kind;
+  if (algorithm.has_value()) {
+    if (*algorithm == "hsfp1") {
+      kind.algorithm = kMapHsfp1;
+    } else if (*algorithm == "blake2s") {
+      kind.algorithm = kMapBlake2s;
+    } else {
+      throw std::invalid_argument(
+          "map_algorithm must be \"hsfp1\" or \"blake2s\"");
+    }
+  }
+  kind.key = key.ptr();
+  return kind;
+}
+
+// The algorithm / key arguments of the fingerprint calls.
+FingerprintKind fingerprint_kind(uint32_t algorithm, const KeyArg& key) {
+  FingerprintKind kind;
+  kind.algorithm = algorithm;
+  if (key.given) {
+    kind.key = key.bytes.data();
+    kind.key_bytes = key.bytes.size();
+  }
+  return kind;
 }
 
 // Runs a call of the delta layer (delta.h), which takes the error string
@@ -674,10 +705,14 @@ PYBIND11_MODULE(_hipstore, m) {
                                 bool overwrite,
                                 std::optional<std::string> base_map,
                                 std::optional<std::string> map_out,
-                                bool compress, std::optional<py::bytes> key) {
+                                bool compress, std::optional<py::bytes> key,
+                                std::optional<std::string> map_algorithm,
+                                std::optional<py::bytes> map_key) {
     DeltaInfo info;
     DeltaMaps maps;
     const KeyArg key_arg(key);
+    const KeyArg map_key_arg(map_key);
+    maps.kind = map_kind(map_algorithm, map_key_arg);
     maps.base_map = base_map.value_or("");
     maps.map_out = map_out.value_or("");
     delta_call("bdev_export_delta", [&](std::string* error) {
@@ -692,11 +727,14 @@ PYBIND11_MODULE(_hipstore, m) {
      py::arg("granule") = py::none(), py::arg("overwrite") = false,
      py::arg("base_map") = py::none(), py::arg("map_out") = py::none(),
      py::arg("compress") = false, py::arg("key") = py::none(),
+     py::arg("map_algorithm") = py::none(), py::arg("map_key") = py::none(),
      "Write the granules of src that differ from base, or from the state "
      "recorded in the fingerprint map base_map (every granule without "
      "either), to a hipstore delta file; map_out also writes the "
      "fingerprint map of src; compress writes a version-2 file of HSLZ1 "
-     "pieces, key (64 bytes) a version-3 file of HSXTS1 ciphertext");
+     "pieces, key (64 bytes) a version-3 file of HSXTS1 ciphertext; "
+     "map_algorithm \"blake2s\" and map_key (32 bytes) make map_out an "
+     "HSFP2 map (base_map decides by itself)");
 
   m.def("xts_encrypt_units", [](py::bytes data, uint32_t granule,
                                 py::bytes key, uint64_t first_unit) {
@@ -984,8 +1022,17 @@ PYBIND11_MODULE(_hipstore, m) {
     return delta_info_to_dict(info);
   }, py::arg("path"), "Header fields of a delta file, after its structural checks");
 
-  m.def("fingerprint_bytes", [](py::bytes data, uint32_t granule) {
+  m.def("fingerprint_bytes", [](py::bytes data, uint32_t granule,
+                                uint32_t algorithm,
+                                std::optional<py::bytes> key) {
     const std::string raw = data;
+    const KeyArg key_arg(key);
+    const FingerprintKind kind = fingerprint_kind(algorithm, key_arg);
+    if (!fingerprint_kind_ok(kind)) {
+      throw std::invalid_argument(
+          "fingerprint_bytes: algorithm 1 or 2 without a key, or 3 with a key "
+          "of 32 bytes");
+    }
     if (granule == 0 || granule % 16 != 0 || raw.size() % granule != 0) {
       throw std::invalid_argument(
           "fingerprint_bytes: granule must be a non-zero multiple of 16 that "
@@ -995,16 +1042,21 @@ PYBIND11_MODULE(_hipstore, m) {
     std::string out(n * kFingerprintBytes, '\0');
     {
       py::gil_scoped_release release;
-      fingerprint_granules(raw.data(), n, granule,
+      fingerprint_granules(raw.data(), n, granule, kind,
                            reinterpret_cast<uint8_t*>(&out[0]));
     }
     return py::bytes(out);
-  }, py::arg("data"), py::arg("granule"),
-     "Granule fingerprints (16 bytes each) of a bytes object, on the host");
+  }, py::arg("data"), py::arg("granule"), py::arg("algorithm") = 1,
+     py::arg("key") = py::none(),
+     "Granule fingerprints (16 bytes each) of a bytes object, on the host: "
+     "algorithm 1 = HSFP1, 2 = HSFP2 (BLAKE2s), 3 = HSFP2 keyed (32 bytes)");
 
   m.def("bdev_fingerprint", [](BdevPtr bdev, uint32_t granule, uint64_t offset,
                                uint64_t length, uint64_t staging_bytes,
-                               bool keep) {
+                               bool keep, uint32_t algorithm,
+                               std::optional<py::bytes> key) {
+    const KeyArg key_arg(key);
+    const FingerprintKind kind = fingerprint_kind(algorithm, key_arg);
     if (length == 0 && granule != 0 && offset <= bdev->size_bytes()) {
       length = (bdev->size_bytes() - offset) / granule * granule;
     }
@@ -1020,7 +1072,8 @@ PYBIND11_MODULE(_hipstore, m) {
                          count * kFingerprintBytes);
             }
             return 0;
-          });
+          },
+          nullptr, kind);
     }
     if (status != kIoOk) {
       throw std::runtime_error("bdev_fingerprint failed: status " +
@@ -1029,24 +1082,32 @@ PYBIND11_MODULE(_hipstore, m) {
     return py::bytes(out);
   }, py::arg("bdev"), py::arg("granule"), py::arg("offset") = 0,
      py::arg("length") = 0, py::arg("staging_bytes") = 0,
-     py::arg("keep") = true,
+     py::arg("keep") = true, py::arg("algorithm") = 1,
+     py::arg("key") = py::none(),
      "Granule fingerprints (16 bytes each) of a bdev range (on-GPU for HBM "
      "bdevs). length=0: to the end of the device in whole granules. "
+     "algorithm and key as fingerprint_bytes. "
      "keep=False discards them and returns b'' (tools/fingerprint_bench.py: "
      "the pass without the host copy)");
 
   m.def("bdev_fingerprint_file", [](BdevPtr bdev, const std::string& path,
                                     std::optional<uint32_t> granule,
-                                    bool overwrite) {
+                                    bool overwrite,
+                                    std::optional<std::string> map_algorithm,
+                                    std::optional<py::bytes> map_key) {
     FingerprintMapInfo info;
+    const KeyArg key_arg(map_key);
+    const MapKind kind = map_kind(map_algorithm, key_arg);
     delta_call("bdev_fingerprint_file", [&](std::string* error) {
       return bdev_fingerprint_file(bdev.get(), path, granule.value_or(0),
-                                   overwrite, &info, error);
+                                   overwrite, &info, error, kind);
     });
     return map_info_to_dict(info);
   }, py::arg("bdev"), py::arg("path"), py::arg("granule") = py::none(),
-     py::arg("overwrite") = false,
-     "Write the fingerprint map of a whole bdev to a file");
+     py::arg("overwrite") = false, py::arg("map_algorithm") = py::none(),
+     py::arg("map_key") = py::none(),
+     "Write the fingerprint map of a whole bdev to a file (map_algorithm "
+     "\"blake2s\": an HSFP2 map, keyed with map_key)");
 
   m.def("fingerprint_map_info", [](const std::string& path) {
     FingerprintMapInfo info;
@@ -1058,10 +1119,15 @@ PYBIND11_MODULE(_hipstore, m) {
      "Header fields of a fingerprint map, after every check of the file");
 
   m.def("bdev_verify_fingerprints", [](BdevPtr bdev, const std::string& path,
-                                       uint32_t max_report) {
+                                       uint32_t max_report,
+                                       std::optional<std::string> map_algorithm,
+                                       std::optional<py::bytes> map_key) {
     FingerprintVerify r;
+    const KeyArg key_arg(map_key);
+    const MapKind kind = map_kind(map_algorithm, key_arg);
     delta_call("bdev_verify_fingerprints", [&](std::string* error) {
-      return bdev_verify_fingerprints(bdev.get(), path, max_report, &r, error);
+      return bdev_verify_fingerprints(bdev.get(), path, max_report, &r, error,
+                                      kind);
     });
     py::dict d;
     d["granule"] = r.granule;
@@ -1070,7 +1136,9 @@ PYBIND11_MODULE(_hipstore, m) {
     d["first_mismatches"] = r.first_mismatches;
     return d;
   }, py::arg("bdev"), py::arg("path"), py::arg("max_report") = 16,
-     "Recompute a bdev's fingerprints over a map's range and compare");
+     py::arg("map_algorithm") = py::none(), py::arg("map_key") = py::none(),
+     "Recompute a bdev's fingerprints over a map's range and compare; a "
+     "keyed map needs its map_key");
 
   m.def("replica_scrub", [](BdevPtr bdev, bool repair, uint32_t granule,
                             uint32_t max_report) {

@@ -91,6 +91,17 @@ def main(argv=None) -> int:
                              help="file of 64 raw bytes on the data-path "
                              "daemon's host: AES-256-XTS key of an "
                              "encrypted checkpoint")
+        if name in ("checkpoint", "verify"):
+            cmd.add_argument("--map-algorithm", default="",
+                             choices=("", "hsfp1", "blake2s"),
+                             help="fingerprints of the map: hsfp1 (the "
+                             "default for a new map) or blake2s "
+                             "(cryptographic); an existing map decides "
+                             "by itself")
+            cmd.add_argument("--map-key-file", default="",
+                             help="file of 32 raw bytes on the data-path "
+                             "daemon's host: key of a keyed blake2s map, "
+                             "which authenticates the volume")
         if name == "restore":
             cmd.add_argument("--dry-run", action="store_true",
                              help="check the file, write nothing")
@@ -176,7 +187,9 @@ def main(argv=None) -> int:
                         bdev_name=args.volume, base_name=args.base,
                         path=args.path, overwrite=args.overwrite,
                         base_map=args.base_map, map_out=args.map_out,
-                        compress=args.compress, key_file=args.key_file),
+                        compress=args.compress, key_file=args.key_file,
+                        map_algorithm=args.map_algorithm,
+                        map_key_file=args.map_key_file),
                     metadata=metadata, timeout=600)
                 print(f"checkpointed {args.volume} -> {args.path}: "
                       f"{reply.saved} of {reply.granules} granules, "
@@ -192,8 +205,10 @@ def main(argv=None) -> int:
                       f"{reply.applied} of {reply.granules} granules")
             elif args.command == "verify":
                 reply = controller.VerifyMallocBDev(
-                    spec.VerifyMallocBDevRequest(bdev_name=args.volume,
-                                                 path=args.path),
+                    spec.VerifyMallocBDevRequest(
+                        bdev_name=args.volume, path=args.path,
+                        map_algorithm=args.map_algorithm,
+                        map_key_file=args.map_key_file),
                     metadata=metadata, timeout=600)
                 print(f"verified {args.volume} against {args.path}: "
                       f"{reply.mismatched} of {reply.granules} granules "

@@ -419,7 +419,9 @@ class Controller(spec.ControllerServicer):
                         base_map=request.base_map or None,
                         map_out=request.map_out or None,
                         compress=request.compress,
-                        key_file=request.key_file or None)
+                        key_file=request.key_file or None,
+                        map_algorithm=request.map_algorithm or None,
+                        map_key_file=request.map_key_file or None)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.CheckpointMallocBDevReply(
@@ -457,7 +459,9 @@ class Controller(spec.ControllerServicer):
                 self._require_bdev(client, name, context)
                 try:
                     result = hipstore.bdev_verify_fingerprints(
-                        client, name, path, max_report=0)
+                        client, name, path, max_report=0,
+                        map_algorithm=request.map_algorithm or None,
+                        map_key_file=request.map_key_file or None)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.VerifyMallocBDevReply(granules=result["granules"],

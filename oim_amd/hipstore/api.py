@@ -332,6 +332,14 @@ def bdev_parity_rebuild(client: Client, data: List[str],
     return client.invoke("bdev_parity_rebuild", params)
 
 
+def _map_params(params: Dict, map_algorithm: Optional[str],
+                map_key_file: Optional[str]) -> None:
+    if map_algorithm is not None:
+        params["map_algorithm"] = map_algorithm
+    if map_key_file is not None:
+        params["map_key_file"] = map_key_file
+
+
 def bdev_export_delta(client: Client, name: str, path: str,
                       base: Optional[str] = None,
                       granule: Optional[int] = None,
@@ -339,7 +347,9 @@ def bdev_export_delta(client: Client, name: str, path: str,
                       base_map: Optional[str] = None,
                       map_out: Optional[str] = None,
                       compress: bool = False,
-                      key_file: Optional[str] = None) -> Dict:
+                      key_file: Optional[str] = None,
+                      map_algorithm: Optional[str] = None,
+                      map_key_file: Optional[str] = None) -> Dict:
     """Checkpoint a volume to a delta file: every granule, or with
     `base` (an earlier clone) or `base_map` (the fingerprint map written
     with an earlier checkpoint; no clone needed) only the granules that
@@ -350,6 +360,11 @@ def bdev_export_delta(client: Client, name: str, path: str,
     `key_file` names a file of exactly 64 raw bytes that the daemon
     reads: every granule is stored AES-256-XTS encrypted (a version-3
     file; not together with compress). The key itself never travels.
+    `map_algorithm` "blake2s" makes `map_out` a map of BLAKE2s
+    fingerprints (HSFP2; default "hsfp1"), `map_key_file` (a file of
+    exactly 32 raw bytes that the daemon reads) a keyed one, which
+    authenticates the volume; with `base_map` that map decides and a
+    keyed one needs its key.
 
     Returns {granule, granules, saved, file_bytes, full}, with map_out
     also map_bytes and with compress stored_bytes (the bytes the granules
@@ -370,6 +385,7 @@ def bdev_export_delta(client: Client, name: str, path: str,
         params["compress"] = True
     if key_file is not None:
         params["key_file"] = key_file
+    _map_params(params, map_algorithm, map_key_file)
     return client.invoke("bdev_export_delta", params)
 
 
@@ -392,30 +408,39 @@ def bdev_import_delta(client: Client, name: str, path: str,
 
 def bdev_fingerprint(client: Client, name: str, path: str,
                      granule: Optional[int] = None,
-                     overwrite: bool = False) -> Dict:
+                     overwrite: bool = False,
+                     map_algorithm: Optional[str] = None,
+                     map_key_file: Optional[str] = None) -> Dict:
     """Write the fingerprint map of a volume (16 bytes per granule) to a
-    file; HBM volumes are hashed on the GPU.
+    file; HBM volumes are hashed on the GPU. `map_algorithm` "blake2s"
+    writes BLAKE2s fingerprints (default "hsfp1"), with `map_key_file`
+    (32 raw bytes, read by the daemon) keyed ones.
 
-    Returns {granule, granules, map_bytes}. granule defaults to the
-    block size."""
+    Returns {granule, granules, map_bytes}, for blake2s also algorithm
+    (2, keyed 3). granule defaults to the block size."""
     params: Dict = {"name": name, "path": path}
     if granule is not None:
         params["granule"] = granule
     if overwrite:
         params["overwrite"] = True
+    _map_params(params, map_algorithm, map_key_file)
     return client.invoke("bdev_fingerprint", params)
 
 
 def bdev_verify_fingerprints(client: Client, name: str, path: str,
-                             max_report: Optional[int] = None) -> Dict:
+                             max_report: Optional[int] = None,
+                             map_algorithm: Optional[str] = None,
+                             map_key_file: Optional[str] = None) -> Dict:
     """Recompute a volume's fingerprints over a map's range and compare
     (verify a restore, scrub for silent corruption). Read-only; on a
-    claimed volume the answer is advisory.
+    claimed volume the answer is advisory. The map decides the algorithm;
+    a keyed map needs its `map_key_file` and then authenticates the volume.
 
     Returns {granule, granules, mismatched, first_mismatches}."""
     params: Dict = {"name": name, "path": path}
     if max_report is not None:
         params["max_report"] = max_report
+    _map_params(params, map_algorithm, map_key_file)
     return client.invoke("bdev_verify_fingerprints", params)
 
 

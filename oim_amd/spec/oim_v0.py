@@ -75,7 +75,9 @@ MESSAGES = [
             [Field("bdev_name", 1, "string"), Field("base_name", 2, "string"),
              Field("path", 3, "string"), Field("overwrite", 4, "bool"),
              Field("base_map", 5, "string"), Field("map_out", 6, "string"),
-             Field("compress", 7, "bool"), Field("key_file", 8, "string")]),
+             Field("compress", 7, "bool"), Field("key_file", 8, "string"),
+             Field("map_algorithm", 9, "string"),
+             Field("map_key_file", 10, "string")]),
     Message("CheckpointMallocBDevReply",
             [Field("granules", 1, "int64"), Field("saved", 2, "int64"),
              Field("file_bytes", 3, "int64")]),
@@ -85,7 +87,9 @@ MESSAGES = [
     Message("RestoreMallocBDevReply",
             [Field("granules", 1, "int64"), Field("applied", 2, "int64")]),
     Message("VerifyMallocBDevRequest",
-            [Field("bdev_name", 1, "string"), Field("path", 2, "string")]),
+            [Field("bdev_name", 1, "string"), Field("path", 2, "string"),
+             Field("map_algorithm", 3, "string"),
+             Field("map_key_file", 4, "string")]),
     Message("VerifyMallocBDevReply",
             [Field("granules", 1, "int64"), Field("mismatched", 2, "int64")]),
     Message("ListMallocBDevsRequest", [Field("prefix", 1, "string")]),

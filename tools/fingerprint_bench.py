@@ -11,6 +11,11 @@ export against the volume's fingerprint map (base_map) and against the
 clone (base), end to end, files included. Prints one JSON line.
 
     python tools/fingerprint_bench.py [--gib 8] [--runs 7] [--dir /tmp]
+        [--algorithm hsfp1 blake2s blake2s-keyed]
+
+With several algorithms (k_blake2s_granules serves both blake2s ones) the
+fingerprint passes alternate in one loop, and the delta exports are timed
+with a map of each.
 
 Host clock around calls that end in a stream synchronise (every call
 also creates and destroys a stream, which is part of either figure).
@@ -43,6 +48,15 @@ def summary(samples, hbm_bytes):
             "read_bytes_per_s": round(hbm_bytes / med)}
 
 
+ALGORITHMS = {  # bdev_fingerprint's, bdev_fingerprint_file's arguments
+    "hsfp1": ({}, {}),
+    "blake2s": ({"algorithm": 2}, {"map_algorithm": "blake2s"}),
+    "blake2s-keyed": ({"algorithm": 3, "key": bytes(range(32))},
+                      {"map_algorithm": "blake2s",
+                       "map_key": bytes(range(32))}),
+}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--gib", type=float, default=8.0, help="volume size")
@@ -52,6 +66,8 @@ def main():
     ap.add_argument("--delta-granule", type=int, default=4096)
     ap.add_argument("--dir", default=None, help="where the files go")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--algorithm", nargs="+", default=["hsfp1"],
+                    choices=sorted(ALGORITHMS))
     args = ap.parse_args()
     if args.runs < 5:
         ap.error("--runs must be at least 5")
@@ -76,8 +92,9 @@ def main():
 
     out = {"bytes": length, "runs": args.runs, "granule": {}}
     for granule in args.granules:
-        def fingerprint():
-            hs.bdev_fingerprint(vol, granule, keep=False)
+        def fingerprint(algorithm=args.algorithm[0]):
+            hs.bdev_fingerprint(vol, granule, keep=False,
+                                **ALGORITHMS[algorithm][0])
 
         def diff():
             hs.bdev_diff(vol, clone, granule=granule, max_report=0)
@@ -85,13 +102,20 @@ def main():
         def diff_self():
             hs.bdev_diff(vol, vol, granule=granule, max_report=0)
 
+        others = args.algorithm[1:]
         for _ in range(2):
             fingerprint()
+            for algorithm in others:
+                fingerprint(algorithm)
             diff()
             diff_self()
         fp_s, diff_s, self_s = [], [], []
+        other_s = {algorithm: [] for algorithm in others}
         for _ in range(args.runs):  # alternate: all see the same neighbours
             fp_s.append(timed(fingerprint))
+            for algorithm in others:
+                other_s[algorithm].append(
+                    timed(lambda: fingerprint(algorithm)))
             diff_s.append(timed(diff))
             self_s.append(timed(diff_self))
         f = summary(fp_s, length)
@@ -101,6 +125,9 @@ def main():
             "bdev_diff_with_itself": summary(self_s, 2 * length),
             "fingerprint_over_diff_rate":
                 round(f["read_bytes_per_s"] / d["read_bytes_per_s"], 3)}
+        for algorithm in others:
+            out["granule"][str(granule)]["bdev_fingerprint_" + algorithm] = \
+                summary(other_s[algorithm], length)
 
     # 1 % changed: delta against the map, against a clone.
     granule = args.delta_granule
@@ -108,8 +135,15 @@ def main():
     with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
         map_path = os.path.join(tmp, "v.map")
         delta = os.path.join(tmp, "v.delta")
-        t_map = timed(lambda: hs.bdev_fingerprint_file(vol, map_path,
-                                                       granule=granule))
+        map_kwargs = ALGORITHMS[args.algorithm[0]][1]
+        t_map = timed(lambda: hs.bdev_fingerprint_file(
+            vol, map_path, granule=granule, **map_kwargs))
+        other_maps = {}
+        for algorithm in args.algorithm[1:]:
+            other_maps[algorithm] = os.path.join(tmp, algorithm + ".map")
+            hs.bdev_fingerprint_file(vol, other_maps[algorithm],
+                                     granule=granule,
+                                     **ALGORITHMS[algorithm][1])
         changed = random.Random(2).sample(range(n), max(1, n // 100))
         bitmap = bytearray((n + 7) // 8)
         for g in changed:
@@ -117,10 +151,19 @@ def main():
         hs.bdev_unpack_marked(vol, bytes(bitmap), granule,
                               b"\xC3" * (len(changed) * granule))
         by_map, by_clone = [], []
+        by_other = {algorithm: [] for algorithm in other_maps}
         saved = set()
+        key = map_kwargs.get("map_key")
         for _ in range(args.runs):
             by_map.append(timed(lambda: saved.add(hs.bdev_export_delta(
-                vol, delta, base_map=map_path, overwrite=True)["marked"])))
+                vol, delta, base_map=map_path, overwrite=True,
+                map_key=key)["marked"])))
+            for algorithm, path in other_maps.items():
+                by_other[algorithm].append(timed(
+                    lambda: saved.add(hs.bdev_export_delta(
+                        vol, delta, base_map=path, overwrite=True,
+                        map_key=ALGORITHMS[algorithm][1].get("map_key"))
+                        ["marked"])))
             by_clone.append(timed(lambda: saved.add(hs.bdev_export_delta(
                 vol, delta, base=clone, granule=granule,
                 overwrite=True)["marked"])))
@@ -130,6 +173,10 @@ def main():
             "base_map_median_ms": round(statistics.median(by_map) * 1e3, 3),
             "base_clone_median_ms":
                 round(statistics.median(by_clone) * 1e3, 3)}
+        for algorithm, samples in by_other.items():
+            out["delta_1pct"]["base_map_median_ms_" + algorithm] = \
+                round(statistics.median(samples) * 1e3, 3)
+        out["algorithm"] = args.algorithm
     print(json.dumps(out))
 
 
