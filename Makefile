@@ -114,17 +114,22 @@ $(B)/parity_test_asan: $(PARITY_TEST_SRCS) $(HDRS) | $(B)
 parity-test: $(B)/parity_test_asan
 	$(B)/parity_test_asan
 
-# Stand-alone check of the HSLZ1 host codec (round trips, malformed
-# streams against the validator and the decoder) under AddressSanitizer
-# and UBSan: host code only, needs no GPU.
+# Stand-alone checks of the HSLZ1 and HSLZD1 host codecs (round trips,
+# malformed streams against the validator and the decoder) under
+# AddressSanitizer and UBSan: host code only, needs no GPU.
 COMPRESS_TEST_SRCS := tests/native/compress_test.cpp native/src/compress.cpp
+DICT_COMPRESS_TEST_SRCS := tests/native/dict_compress_test.cpp native/src/compress.cpp
 
 $(B)/compress_test_asan: $(COMPRESS_TEST_SRCS) $(HDRS) | $(B)
 	$(HIPCC) $(CXXFLAGS) -O1 -g -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(COMPRESS_TEST_SRCS) -o $@
 
+$(B)/dict_compress_test_asan: $(DICT_COMPRESS_TEST_SRCS) $(HDRS) | $(B)
+	$(HIPCC) $(CXXFLAGS) -O1 -g -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(DICT_COMPRESS_TEST_SRCS) -o $@
+
 .PHONY: compress-test
-compress-test: $(B)/compress_test_asan
+compress-test: $(B)/compress_test_asan $(B)/dict_compress_test_asan
 	$(B)/compress_test_asan
+	$(B)/dict_compress_test_asan
 
 # Stand-alone check of the HSXTS1 host codec (FIPS-197 and XTS known
 # answers, round trips, the equivalent-inverse schedule, kcv) under

@@ -1,5 +1,6 @@
-// Compressed checkpoints: the HSLZ1 granule codec and the marked
-// compress / decompress calls under version-2 delta files (delta.h).
+// Compressed checkpoints: the HSLZ1 and HSLZD1 granule codecs and the
+// marked compress / decompress calls under version-2 and version-4 delta
+// files (delta.h).
 //
 // HSLZ1. A granule of G bytes (512 <= G <= 16384, G % 16 == 0) is
 // compressed on its own and stored either as a legal LZ4 block (token,
@@ -29,6 +30,30 @@
 //     equal; the sequence (literals [anchor, q), offset q - c, length) is
 //     emitted; anchor = p = q + length.
 //   - The bytes from anchor to G are emitted as the final literals.
+//
+// HSLZD1 (version-4 delta files) compresses a granule X against a
+// dictionary D of the same G bytes: the base granule of an incremental
+// checkpoint. The image is B = D || X, positions 0 .. 2G - 1 (all fit 16
+// bits). A stored piece is a legal LZ4 block that a decoder with D as
+// prefix history turns into X (offsets reach back up to G + the bytes
+// produced so far) or, when that block would not be smaller than G, the
+// raw X. A stored size of G means raw, as in HSLZ1.
+//
+// The parse is HSLZ1's over B with these changes and no others:
+//   - seeding: before the scan every position q < G is inserted into the
+//     table under hash(u32 of B at q), so the last three read into X; a
+//     slot takes the greatest position inserted.
+//   - anchor = p = G; a window is q = p + l, 0 <= l < 64, q <= 2G - 12.
+//   - the candidate of q is the aligned position q - G when the u32
+//     there equals the u32 at q; otherwise the table candidate under
+//     HSLZ1's rule. The aligned candidate needs no table and collisions
+//     cannot displace it: a dictionary position i survives the seeding
+//     only with probability about exp(-(G - i) / 2048).
+//   - winner, inserts, extension (while q + length < 2G - 5), emission
+//     and final literals are HSLZ1's with 2G for G; literal lengths and
+//     the stored-size bound are relative to G (the output is X alone).
+// lz_dict_compress_granule and k_lzd_compress_marked emit identical
+// bytes.
 
 #pragma once
 
@@ -77,6 +102,20 @@ bool lz_decompress_granule(const uint8_t* piece, uint64_t size,
                            uint32_t granule, uint8_t* out,
                            std::string* why = nullptr);
 
+// The same three for HSLZD1. in, dict and out hold `granule` bytes each
+// and out overlaps neither. The validator is the same token walk with
+// offsets >= 1 and <= granule + the bytes produced so far: it needs no
+// dictionary bytes. The decoder never reads outside the piece or dict[0,
+// granule) and never writes outside out; with another dictionary than
+// the compressor's it gives other bytes, not an error.
+uint32_t lz_dict_compress_granule(const uint8_t* in, const uint8_t* dict,
+                                  uint32_t granule, uint8_t* out);
+bool lz_dict_validate_granule(const uint8_t* piece, uint64_t size,
+                              uint32_t granule, std::string* why = nullptr);
+bool lz_dict_decompress_granule(const uint8_t* piece, uint64_t size,
+                                uint32_t granule, const uint8_t* dict,
+                                uint8_t* out, std::string* why = nullptr);
+
 // bdev_pack_marked_sync with every granule compressed: sink(data, sizes,
 // first_rank, count) receives the stored sizes of marked granules
 // first_rank .. first_rank + count - 1 and their pieces in `data`, piece
@@ -116,5 +155,35 @@ int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 const DecompressSource& source,
                                 uint64_t* unpacked = nullptr,
                                 std::string* error = nullptr);
+
+// bdev_compress_marked_sync with HSLZD1: granule g of the range of `src`
+// is compressed against granule g of the range of `base` (same block
+// size, both ranges valid). The kernel path (k_lzd_compress_marked)
+// applies when both are HBM-resident and reachable from one device, as
+// for bdev_diff_sync; otherwise both are read through the bdev interface
+// in spans of at most 1 MiB and lz_dict_compress_granule does the work.
+// Same chunks and bytes on both paths. Ranges that overlap in one
+// backing store are kIoInvalid, as in bdev_copy_marked_sync.
+int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
+                                   uint64_t base_offset, uint64_t length,
+                                   uint32_t granule,
+                                   const std::vector<uint64_t>& bitmap,
+                                   uint64_t staging_bytes,
+                                   const CompressSink& sink,
+                                   uint64_t* packed = nullptr,
+                                   std::string* error = nullptr);
+
+// bdev_decompress_marked_sync with HSLZD1: the dictionary of a granule is
+// what the target holds there when the call reaches it, so the target
+// must be at the base state and the call is not idempotent. Pieces are
+// checked with lz_dict_validate_granule first. k_lzd_decompress_marked
+// reads a granule into LDS before it overwrites it and touches no other.
+int bdev_dict_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
+                                     uint64_t length, uint32_t granule,
+                                     const std::vector<uint64_t>& bitmap,
+                                     uint64_t staging_bytes,
+                                     const DecompressSource& source,
+                                     uint64_t* unpacked = nullptr,
+                                     std::string* error = nullptr);
 
 }  // namespace hipstore

@@ -46,6 +46,27 @@
 // There is no authentication (a CRC is not a MAC), and a key together
 // with `compress` is refused: compress-then-encrypt needs padding or
 // ciphertext stealing.
+//
+// "hipstore delta file, version 4" holds the granules of an incremental
+// compressed against the base (HSLZD1, compress.h: the dictionary of a
+// granule is the same granule of the base volume) and is what an export
+// with `compress`, `dictionary` and a clone as `base` writes. The layout
+// is exactly version 2's (header, bitmap, var records, record_area_bytes,
+// trailer) with
+//   - version = 4 and flags bit 1 (kDeltaFlagLz) and bit 3
+//     (kDeltaFlagDict) both set; version 4 if and only if bit 3, and bit 3
+//     implies bit 1
+// and the import checks are version 2's too: the validator needs no
+// dictionary bytes, so the structural pass, the record CRCs, the host
+// validation of every piece before it reaches the GPU and dry_run work as
+// for version 2. The dictionary of a granule at import is what the target
+// holds there, so a version-4 import is NOT idempotent: after a bad
+// record or a second application the granules already written are no
+// longer the dictionary. The file does not identify its base (as no delta
+// file does), with sharper consequences: applied to a volume that is not
+// at the base state it decodes memory-safely into wrong data. A map_out
+// map of the export plus bdev_verify_fingerprints after the import is the
+// check.
 
 #pragma once
 
@@ -63,6 +84,8 @@ constexpr uint32_t kDeltaFlagFull = 1;
 constexpr uint32_t kDeltaVersionXts = 3;
 constexpr uint32_t kDeltaFlagLz = 2;
 constexpr uint32_t kDeltaFlagXts = 4;
+constexpr uint32_t kDeltaVersionDict = 4;
+constexpr uint32_t kDeltaFlagDict = 8;
 constexpr uint64_t kDeltaHeaderBytes = 64;
 constexpr uint64_t kDeltaTrailerBytes = 16;
 constexpr uint64_t kDeltaRecordBytes = 1ull << 20;
@@ -81,6 +104,7 @@ struct DeltaInfo {
   // of the stored sizes of a compressed file.
   uint64_t stored_bytes = 0;
   bool encrypted = false;  // version 3
+  bool dictionary = false;  // version 4 (then also compressed)
 };
 
 // Every call returns an IoStatus and, on failure, a one-line reason in
@@ -237,6 +261,12 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
 // length, with equal halves, or together with `compress` is kIoInvalid).
 // `base`, `base_map` and `map_out` work unchanged with it.
 //
+// `dictionary` writes a version-4 file: every granule is compressed
+// against the same granule of `base`. It needs `compress` and `base` (a
+// clone, whose bytes are the dictionaries): without `compress`, without
+// `base` (a full export or `base_map`, which has no base bytes) or
+// together with `key` it is kIoInvalid before anything is written.
+//
 // `kind` says which fingerprints the maps hold. With `base_map`, the pass
 // and `map_out` take the base map's algorithm and the rules of
 // bdev_verify_fingerprints apply; without, `map_out` is written as `kind`
@@ -252,6 +282,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
                       DeltaInfo* stats, std::string* error,
                       bool compress = false,
-                      const std::vector<uint8_t>* key = nullptr);
+                      const std::vector<uint8_t>* key = nullptr,
+                      bool dictionary = false);
 
 }  // namespace hipstore

@@ -49,8 +49,8 @@ uint64_t record_stream_bytes(uint64_t total, uint64_t unit,
 }
 
 int InFile::open(const std::string& path, const Format& format,
-                 std::string* error, const Format* newer,
-                 const Format* newest) {
+                 std::string* error,
+                 std::initializer_list<const Format*> later) {
   format_ = &format;
   in_.fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
   if (in_.fd < 0) return fail(error, kIoFailed, errno_text("open " + path));
@@ -73,11 +73,10 @@ int InFile::open(const std::string& path, const Format& format,
   if (get_u32(h + 60) != crc32c_sw(0, h, 60)) {
     return fail(error, kIoInvalid, "header CRC mismatch");
   }
-  if (newer != nullptr && get_u32(h + 8) == newer->version) {
-    format_ = newer;
-  } else if (newest != nullptr && get_u32(h + 8) == newest->version) {
-    format_ = newest;
-  } else if (get_u32(h + 8) != format.version) {
+  for (const Format* f : later) {
+    if (get_u32(h + 8) == f->version) format_ = f;
+  }
+  if (get_u32(h + 8) != format_->version) {
     return fail(error, kIoInvalid, "unsupported " + noun + " version");
   }
   header.block_size = get_u32(h + 12);

@@ -11,6 +11,7 @@
 #pragma once
 
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -95,10 +96,10 @@ class InFile {
  public:
   // Checks, in this order: regular file, room for header and trailer,
   // magic, header CRC, version. kIoFailed when the file cannot be opened.
-  // `newer` and `newest` are later versions of the same format (same
-  // magics) that are accepted too; format() tells which one the file is.
+  // `later` are later versions of the same format (same magics) that are
+  // accepted too; format() tells which one the file is.
   int open(const std::string& path, const Format& format, std::string* error,
-           const Format* newer = nullptr, const Format* newest = nullptr);
+           std::initializer_list<const Format*> later = {});
   const Format& format() const { return *format_; }
   // The file is exactly header, `body` bytes and trailer.
   int check_length(uint64_t body, std::string* error) const;

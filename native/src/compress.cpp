@@ -1,11 +1,13 @@
-// The HSLZ1 granule codec on the host (hipstore/compress.h): the
-// normative parse, byte for byte what k_lz_compress_marked emits, the
-// validator and the decoder. Plain host code; the marked calls and the
-// kernels are in compress_ops.hip.
+// The HSLZ1 and HSLZD1 granule codecs on the host (hipstore/compress.h):
+// the normative parse, byte for byte what k_lz_compress_marked and
+// k_lzd_compress_marked emit, the validator and the decoder. Plain host
+// code; the marked calls and the kernels are in compress_ops.hip.
 
 #include "hipstore/compress.h"
 
 #include <string.h>
+
+#include <vector>
 
 namespace hipstore {
 
@@ -35,8 +37,11 @@ bool refuse(std::string* why, const char* what) {
 }
 
 // One token walk for the validator (out == nullptr) and the decoder.
+// `history` is what lies before the granule: 0 for HSLZ1, the granule
+// size for HSLZD1, whose decoder reads those bytes from `dict`.
 bool lz_walk(const uint8_t* piece, uint64_t size, uint32_t granule,
-             uint8_t* out, std::string* why) {
+             uint64_t history, const uint8_t* dict, uint8_t* out,
+             std::string* why) {
   if (!lz_granule_ok(granule)) return refuse(why, "unsupported granule");
   if (size == 0 || size > granule) return refuse(why, "stored size out of range");
   if (size == granule) {
@@ -76,26 +81,34 @@ bool lz_walk(const uint8_t* piece, uint64_t size, uint32_t granule,
     const uint64_t offset = piece[ip] | static_cast<uint64_t>(piece[ip + 1]) << 8;
     ip += 2;
     if (offset == 0) return refuse(why, "offset 0");
-    if (offset > op) return refuse(why, "offset past the start of the granule");
+    if (offset > history + op) {
+      return refuse(why, history != 0 ? "offset past the start of the dictionary"
+                                      : "offset past the start of the granule");
+    }
     uint64_t len = 0;
     if (!length(token & 15, &len)) return refuse(why, "truncated match length");
     len += 4;
     if (op > granule - 12) return refuse(why, "match starts after granule - 12");
     if (len > granule - 5 - op) return refuse(why, "match overruns granule - 5");
     if (out != nullptr) {
-      for (uint64_t i = 0; i < len; ++i) out[op + i] = out[op + i - offset];
+      for (uint64_t i = 0; i < len; ++i) {
+        const uint64_t at = history + op + i - offset;  // in dict || out
+        out[op + i] = at >= history ? out[at - history] : dict[at];
+      }
     }
     op += len;
   }
 }
 
-}  // namespace
-
-uint32_t lz_compress_granule(const uint8_t* in, uint32_t granule,
-                             uint8_t* out) {
-  uint32_t table[1u << kLzHashBits] = {0};  // position + 1, 0 = empty
-  const uint32_t last = granule - 12;  // last position a match may start at
-  uint32_t anchor = 0;
+// The parse of compress.h over image[0, start + granule): the granule is
+// image[start, start + granule), what lies before it is history that
+// `table` (position + 1, 0 = empty) already holds. `aligned` adds
+// HSLZD1's candidate q - granule.
+uint32_t lz_parse(const uint8_t* image, uint32_t start, uint32_t granule,
+                  bool aligned, uint32_t* table, uint8_t* out) {
+  const uint32_t end = start + granule;
+  const uint32_t last = end - 12;  // last position a match may start at
+  uint32_t anchor = start;
   uint32_t op = 0;
   // Literals [anchor, anchor + lit), then a match unless len == 0.
   // false: the block would not be smaller than the granule.
@@ -107,7 +120,7 @@ uint32_t lz_compress_granule(const uint8_t* in, uint32_t granule,
     uint8_t* o = out + op;
     *o++ = static_cast<uint8_t>((lit < 15 ? lit : 15) << 4 | (ml < 15 ? ml : 15));
     o = put_ext(o, lit);
-    memcpy(o, in + anchor, lit);
+    memcpy(o, image + anchor, lit);
     o += lit;
     if (len != 0) {
       *o++ = static_cast<uint8_t>(offset);
@@ -118,21 +131,25 @@ uint32_t lz_compress_granule(const uint8_t* in, uint32_t granule,
     return true;
   };
   bool fits = true;
-  for (uint32_t p = 0; fits && p <= last;) {
+  for (uint32_t p = start; fits && p <= last;) {
     const uint32_t lanes = last - p + 1 < kLzWindow ? last - p + 1 : kLzWindow;
     uint32_t winner = lanes;
     uint32_t cand = 0;
     for (uint32_t l = 0; l < lanes && winner == lanes; ++l) {
-      const uint32_t v = load_u32(in + p + l);
+      const uint32_t q = p + l;
+      const uint32_t v = load_u32(image + q);
       const uint32_t slot = table[lz_hash(v)];
-      if (slot != 0 && load_u32(in + slot - 1) == v) {
+      if (aligned && load_u32(image + q - granule) == v) {
+        winner = l;
+        cand = q - granule;
+      } else if (slot != 0 && load_u32(image + slot - 1) == v) {
         winner = l;
         cand = slot - 1;
       }
     }
     // Ascending, so a slot ends up with the greatest position.
     for (uint32_t l = 0; l < lanes && l <= winner; ++l) {
-      table[lz_hash(load_u32(in + p + l))] = p + l + 1;
+      table[lz_hash(load_u32(image + p + l))] = p + l + 1;
     }
     if (winner == lanes) {
       p += kLzWindow;
@@ -140,26 +157,58 @@ uint32_t lz_compress_granule(const uint8_t* in, uint32_t granule,
     }
     const uint32_t q = p + winner;
     uint32_t len = 4;
-    while (q + len < granule - 5 && in[cand + len] == in[q + len]) ++len;
+    while (q + len < end - 5 && image[cand + len] == image[q + len]) ++len;
     fits = emit(q - anchor, q - cand, len);
     anchor = p = q + len;
   }
-  if (fits) fits = emit(granule - anchor, 0, 0);
+  if (fits) fits = emit(end - anchor, 0, 0);
   if (!fits) {
-    memcpy(out, in, granule);
+    memcpy(out, image + start, granule);
     return granule;
   }
   return op;
 }
 
+}  // namespace
+
+uint32_t lz_compress_granule(const uint8_t* in, uint32_t granule,
+                             uint8_t* out) {
+  uint32_t table[1u << kLzHashBits] = {0};
+  return lz_parse(in, 0, granule, false, table, out);
+}
+
+uint32_t lz_dict_compress_granule(const uint8_t* in, const uint8_t* dict,
+                                  uint32_t granule, uint8_t* out) {
+  std::vector<uint8_t> image(2 * static_cast<size_t>(granule));
+  memcpy(image.data(), dict, granule);
+  memcpy(image.data() + granule, in, granule);
+  uint32_t table[1u << kLzHashBits] = {0};
+  // Ascending, so a slot ends up with the greatest position.
+  for (uint32_t q = 0; q < granule; ++q) {
+    table[lz_hash(load_u32(image.data() + q))] = q + 1;
+  }
+  return lz_parse(image.data(), granule, granule, true, table, out);
+}
+
 bool lz_validate_granule(const uint8_t* piece, uint64_t size, uint32_t granule,
                          std::string* why) {
-  return lz_walk(piece, size, granule, nullptr, why);
+  return lz_walk(piece, size, granule, 0, nullptr, nullptr, why);
 }
 
 bool lz_decompress_granule(const uint8_t* piece, uint64_t size,
                            uint32_t granule, uint8_t* out, std::string* why) {
-  return lz_walk(piece, size, granule, out, why);
+  return lz_walk(piece, size, granule, 0, nullptr, out, why);
+}
+
+bool lz_dict_validate_granule(const uint8_t* piece, uint64_t size,
+                              uint32_t granule, std::string* why) {
+  return lz_walk(piece, size, granule, granule, nullptr, nullptr, why);
+}
+
+bool lz_dict_decompress_granule(const uint8_t* piece, uint64_t size,
+                                uint32_t granule, const uint8_t* dict,
+                                uint8_t* out, std::string* why) {
+  return lz_walk(piece, size, granule, granule, dict, out, why);
 }
 
 }  // namespace hipstore

@@ -22,6 +22,17 @@
 // slots), decompress 2 * G (piece, image). A workgroup has the 4, 2 or 1
 // waves that fit 64 KiB: compress 4 waves up to G = 4096 (64 KiB at
 // 4096), 2 up to 12288, 1 above; decompress 4 up to 8192, 2 above.
+//
+// HSLZD1 (k_lzd_compress_marked, k_lzd_decompress_marked): the same split
+// and movement with the base granule as dictionary. Compress holds the
+// image D || X, the block and the table, 3 * G + 8 KiB per wave: D comes
+// from the base volume, the table is seeded from it, and the scan runs
+// over X with an aligned candidate that needs no table. Decompress holds
+// the piece and the image, 3 * G: it reads its target granule as D,
+// decodes behind it and only then overwrites the granule. A workgroup has
+// as many waves, 1 .. 4, as fit 64 KiB: compress 4 up to G = 2720, 3 up
+// to 4544, 2 up to 8192, 1 above; decompress 4 up to 5456, 3 up to 7280,
+// 2 up to 10912, 1 above.
 
 #include <hip/hip_runtime.h>
 
@@ -110,15 +121,20 @@ __device__ __forceinline__ bool lz_emit(const uint8_t* in, uint8_t* out,
 
 // The parse of compress.h over the LDS image `in`; the block goes to
 // `out`. Returns the stored size, `granule` for raw. Everything but the
-// per-lane candidate test is wave-uniform.
+// per-lane candidate test is wave-uniform. kDict is HSLZD1: `in` is
+// D || X, `table` holds the positions of D, the scan starts at G and a
+// lane first tries its aligned position q - G, which needs no table.
+template <bool kDict>
 __device__ __forceinline__ uint32_t lz_parse(const uint8_t* in, uint8_t* out,
                                              uint32_t* table, uint32_t granule,
                                              uint32_t lane) {
   const uint32_t* in32 = reinterpret_cast<const uint32_t*>(in);
-  const uint32_t last = granule - 12;
-  uint32_t anchor = 0;
+  const uint32_t start = kDict ? granule : 0;
+  const uint32_t end = start + granule;
+  const uint32_t last = end - 12;
+  uint32_t anchor = start;
   uint32_t op = 0;
-  uint32_t p = 0;
+  uint32_t p = start;
   while (p <= last) {
     const uint32_t q = p + lane;
     const bool live = q <= last;
@@ -129,7 +145,10 @@ __device__ __forceinline__ uint32_t lz_parse(const uint8_t* in, uint8_t* out,
       const uint32_t v = lds_u32(in32, q);
       hash = (v * kLzHashMul) >> (32 - kLzHashBits);
       const uint32_t slot = table[hash];  // position + 1, 0 = empty
-      if (slot != 0) {
+      if (kDict && lds_u32(in32, q - granule) == v) {
+        cand = q - granule;
+        hit = true;
+      } else if (slot != 0) {
         cand = slot - 1;
         hit = lds_u32(in32, cand) == v;
       }
@@ -148,7 +167,7 @@ __device__ __forceinline__ uint32_t lz_parse(const uint8_t* in, uint8_t* out,
     const uint32_t wc = static_cast<uint32_t>(
         __shfl(static_cast<int>(cand), static_cast<int>(winner)));
     // 64 bytes per step; the first lane that must stop ends the match.
-    const uint32_t cap = granule - 5 - wq;  // >= 7: wq <= granule - 12
+    const uint32_t cap = end - 5 - wq;  // >= 7: wq <= end - 12
     uint32_t len = 4;
     for (;;) {
       const uint32_t i = len + lane;
@@ -166,7 +185,7 @@ __device__ __forceinline__ uint32_t lz_parse(const uint8_t* in, uint8_t* out,
     }
     anchor = p = wq + len;
   }
-  if (!lz_emit(in, out, op, anchor, granule - anchor, 0, 0, granule, lane)) {
+  if (!lz_emit(in, out, op, anchor, end - anchor, 0, 0, granule, lane)) {
     return granule;
   }
   return op;
@@ -200,7 +219,7 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_compress_marked(
       table16[i] = make_uint4(0, 0, 0, 0);
     }
     wave_sync();
-    const uint32_t size = lz_parse(in, out, table, granule, lane);
+    const uint32_t size = lz_parse<false>(in, out, table, granule, lane);
     // size < granule and granule % 16 == 0: the pad stays inside `out`.
     if (size != granule && lane < ((16 - (size & 15)) & 15)) {
       out[size + lane] = 0;
@@ -208,6 +227,65 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_compress_marked(
     wave_sync();
     const uint4* from =
         size == granule ? in16 : reinterpret_cast<const uint4*>(out);
+    uint4* __restrict__ ps = reinterpret_cast<uint4*>(
+        scratch + static_cast<uint64_t>(slot) * granule);
+    for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) ps[i] = from[i];
+    if (lane == 0) sizes[slot] = size;
+    wave_sync();  // the next granule overwrites this LDS
+  });
+}
+
+// k_lz_compress_marked with HSLZD1: granule g of `base` is the
+// dictionary of granule g of `src`. Per-wave LDS: the image D || X (2G,
+// D immediately before X, so a u32 that straddles the boundary and a
+// match that runs from D into X are plain addressing), the block (G) and
+// the table. The table is cleared, then seeded with the positions of D
+// in rows of 64: atomicMax of position + 1 leaves the greatest position
+// in a slot whatever the order. Slots, pad and sizes as above.
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_compress_marked(
+    const uint8_t* __restrict__ src, const uint8_t* __restrict__ base,
+    uint8_t* __restrict__ scratch, uint32_t* __restrict__ sizes,
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule) {
+  extern __shared__ uint4 lz_lds[];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule >> 4;
+  uint8_t* image = reinterpret_cast<uint8_t*>(lz_lds) +
+                   (threadIdx.x >> 6) * (3 * granule + kLzTableBytes);
+  uint8_t* out = image + 2 * granule;
+  uint32_t* table = reinterpret_cast<uint32_t*>(out + granule);
+  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
+                                                      uint32_t slot) {
+    const uint4* __restrict__ pd =
+        reinterpret_cast<const uint4*>(base + g * granule);
+    const uint4* __restrict__ px =
+        reinterpret_cast<const uint4*>(src + g * granule);
+    uint4* image16 = reinterpret_cast<uint4*>(image);
+    uint4* table16 = reinterpret_cast<uint4*>(table);
+#pragma unroll 4
+    for (uint32_t i = lane; i < n16; i += 64) {
+      image16[i] = pd[i];
+      image16[n16 + i] = px[i];
+    }
+    for (uint32_t i = lane; i < kLzTableBytes / 16; i += 64) {
+      table16[i] = make_uint4(0, 0, 0, 0);
+    }
+    wave_sync();
+    const uint32_t* image32 = reinterpret_cast<const uint32_t*>(image);
+    for (uint32_t q = lane; q < granule; q += 64) {  // q + 8 <= 2G
+      const uint32_t v = lds_u32(image32, q);
+      atomicMax(&table[(v * kLzHashMul) >> (32 - kLzHashBits)], q + 1);
+    }
+    wave_sync();
+    const uint32_t size = lz_parse<true>(image, out, table, granule, lane);
+    // size < granule and granule % 16 == 0: the pad stays inside `out`.
+    if (size != granule && lane < ((16 - (size & 15)) & 15)) {
+      out[size + lane] = 0;
+    }
+    wave_sync();
+    const uint4* from = size == granule ? image16 + n16
+                                        : reinterpret_cast<const uint4*>(out);
     uint4* __restrict__ ps = reinterpret_cast<uint4*>(
         scratch + static_cast<uint64_t>(slot) * granule);
     for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) ps[i] = from[i];
@@ -254,27 +332,29 @@ __device__ __forceinline__ bool lz_take_ext(const uint8_t* piece,
   }
 }
 
-// Decodes piece[0, size), size < G, into image[0, G). Every read of the
-// piece is checked against `size` and every write of the image against
-// G before it happens; a sequence that would leave either ends the
-// decode with false. A match reads image[op - offset + (i mod offset)],
-// which lies below op for every i: correct down to offset 1 without any
-// order among the lanes.
+// Decodes piece[0, size), size < G, into image[start, end), end = start
+// + G; image[0, start) is history that matches may reach into (HSLZD1's
+// dictionary; start = 0 for HSLZ1). Every read of the piece is checked
+// against `size`, every write of the image against `end` and every
+// offset against op before it happens; a sequence that would leave any
+// of them ends the decode with false. A match reads image[op - offset +
+// (i mod offset)], which lies below op for every i: correct down to
+// offset 1 without any order among the lanes.
 __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
-                                          uint8_t* image, uint32_t granule,
-                                          uint32_t lane) {
+                                          uint8_t* image, uint32_t start,
+                                          uint32_t end, uint32_t lane) {
   uint32_t ip = 0;
-  uint32_t op = 0;
+  uint32_t op = start;
   for (;;) {
     if (ip >= size) return false;
     const uint32_t token = lz_byte(piece, ip++);
     uint32_t lit = token >> 4;
     if (lit == 15 && !lz_take_ext(piece, size, ip, lit)) return false;
-    if (lit > size - ip || lit > granule - op) return false;
+    if (lit > size - ip || lit > end - op) return false;
     for (uint32_t i = lane; i < lit; i += 64) image[op + i] = piece[ip + i];
     ip += lit;
     op += lit;
-    if (ip == size) return op == granule;
+    if (ip == size) return op == end;
     if (size - ip < 2) return false;
     const uint32_t offset = lz_byte(piece, ip) | lz_byte(piece, ip + 1) << 8;
     ip += 2;
@@ -282,7 +362,7 @@ __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
     uint32_t len = token & 15;
     if (len == 15 && !lz_take_ext(piece, size, ip, len)) return false;
     len += 4;
-    if (len > granule - op) return false;
+    if (len > end - op) return false;
     wave_sync();  // the literals above may be the match's source
     const uint32_t from = op - offset;
     const uint32_t step = 64 % offset;
@@ -327,11 +407,57 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
       for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) piece16[i] = pp[i];
       wave_sync();
       ok = lz_decode(reinterpret_cast<const uint8_t*>(piece16), size,
-                     reinterpret_cast<uint8_t*>(image16), granule, lane);
+                     reinterpret_cast<uint8_t*>(image16), 0, granule, lane);
       wave_sync();
       if (ok) {
 #pragma unroll 4
         for (uint32_t i = lane; i < n16; i += 64) pd[i] = image16[i];
+      }
+      wave_sync();  // the next piece overwrites this LDS
+    }
+    if (lane == 0) bad[slot] = ok ? 0 : 1;
+  });
+}
+
+// k_lz_decompress_marked with HSLZD1: the dictionary of a piece is what
+// its granule of `dst` holds now. Per-wave LDS: the piece (G) and the
+// image (2G). The wave reads the granule into image[0, G), decodes into
+// image[G, 2G) and only then writes the granule, so it reads its target
+// before it overwrites it; it touches no other granule, so waves need no
+// order. A raw piece is copied straight and reads nothing of `dst`.
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_decompress_marked(
+    uint8_t* dst, const uint8_t* __restrict__ dense,
+    const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
+    uint8_t* __restrict__ bad, const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule) {
+  extern __shared__ uint4 lz_lds[];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule >> 4;
+  uint4* piece16 = lz_lds + (threadIdx.x >> 6) * (3 * n16);
+  uint4* image16 = piece16 + n16;
+  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
+                                                      uint32_t slot) {
+    const uint32_t size = uniform(sizes[slot]);
+    const uint4* __restrict__ pp =
+        reinterpret_cast<const uint4*>(dense + offsets[slot]);
+    uint4* pd = reinterpret_cast<uint4*>(dst + g * granule);
+    bool ok = size != 0 && size <= granule;
+    if (size == granule) {  // raw
+#pragma unroll 4
+      for (uint32_t i = lane; i < n16; i += 64) pd[i] = pp[i];
+    } else if (ok) {
+      for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) piece16[i] = pp[i];
+#pragma unroll 4
+      for (uint32_t i = lane; i < n16; i += 64) image16[i] = pd[i];
+      wave_sync();
+      ok = lz_decode(reinterpret_cast<const uint8_t*>(piece16), size,
+                     reinterpret_cast<uint8_t*>(image16), granule, 2 * granule,
+                     lane);
+      wave_sync();
+      if (ok) {
+#pragma unroll 4
+        for (uint32_t i = lane; i < n16; i += 64) pd[i] = image16[n16 + i];
       }
       wave_sync();  // the next piece overwrites this LDS
     }
@@ -346,6 +472,11 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
 // Waves per workgroup for `per_wave` bytes of LDS each.
 uint32_t lz_waves(uint32_t per_wave) {
   return 4 * per_wave <= kLzMaxLds ? 4 : 2 * per_wave <= kLzMaxLds ? 2 : 1;
+}
+
+// The HSLZD1 kernels take as many waves, 1 .. 4, as fit.
+uint32_t lzd_waves(uint32_t per_wave) {
+  return std::min<uint32_t>(4, kLzMaxLds / per_wave);
 }
 
 // Device memory that grows on demand and keeps what it has, like
@@ -419,12 +550,15 @@ uint64_t granule_of_rank(const std::vector<uint64_t>& bitmap, uint64_t rank) {
 // fills `offsets`. kIoInvalid names the granule.
 int check_window(const std::vector<uint64_t>& bitmap, const uint8_t* data,
                  const uint32_t* sizes, uint64_t first_rank, uint64_t count,
-                 uint32_t granule, uint64_t* offsets, std::string* error) {
+                 uint32_t granule, bool dictionary, uint64_t* offsets,
+                 std::string* error) {
   uint64_t at = 0;
   for (uint64_t i = 0; i < count; ++i) {
     std::string why = "stored size out of range";
     if (sizes[i] == 0 || sizes[i] > granule ||
-        !lz_validate_granule(data + at, sizes[i], granule, &why)) {
+        !(dictionary
+              ? lz_dict_validate_granule(data + at, sizes[i], granule, &why)
+              : lz_validate_granule(data + at, sizes[i], granule, &why))) {
       if (error != nullptr) {
         *error = "granule " +
                  std::to_string(granule_of_rank(bitmap, first_rank + i)) +
@@ -439,7 +573,9 @@ int check_window(const std::vector<uint64_t>& bitmap, const uint8_t* data,
 }
 
 // What both GPU window loops run on: HalvesStream's `done` events end a
-// half's last kernel, `packed` ends k_lz_compress_marked alone.
+// half's last kernel, `packed` ends k_lz_compress_marked alone. With
+// `dictionary` the HSLZD1 kernels run: compress reads the dictionaries
+// at `dict`, decompress takes them from the target itself.
 struct LzStream : HalvesStream {
   hipEvent_t packed[2] = {nullptr, nullptr};
   uint32_t granule;
@@ -452,9 +588,12 @@ struct LzStream : HalvesStream {
   const unsigned long long* dev_words;
   const uint32_t* dev_ranks;
   uint8_t* base;  // the bdev's range in device memory
+  bool dictionary;
+  const uint8_t* dict;  // the base volume's range in device memory
 
   LzStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
-           const MarkedPlan& plan, bool compress)
+           const MarkedPlan& plan, bool compress, bool with_dictionary = false,
+           const uint8_t* dict_range = nullptr)
       : HalvesStream(device), granule(granule_bytes),
         chunk(plan.chunk_granules),
         dense(compress_ctx().dense.reserve(2 * chunk * granule)),
@@ -462,7 +601,8 @@ struct LzStream : HalvesStream {
         offsets(compress_ctx().offsets.reserve(2 * chunk)),
         bad(compress_ctx().bad.reserve(2 * chunk)),
         dev_words(device_view(plan.words)), dev_ranks(device_view(plan.ranks)),
-        base(static_cast<uint8_t*>(bdev->device_base()) + offset) {
+        base(static_cast<uint8_t*>(bdev->device_base()) + offset),
+        dictionary(with_dictionary), dict(dict_range) {
     if (compress) {
       scratch = compress_ctx().scratch.reserve(device, 2 * chunk * granule);
       for (hipEvent_t& e : packed) {
@@ -478,13 +618,25 @@ struct LzStream : HalvesStream {
   }
 
   void compress(const MarkedWindow& win, int half) {
-    const uint32_t per_wave = 2 * granule + kLzTableBytes;
-    const uint32_t waves = lz_waves(per_wave);
-    hipLaunchKernelGGL(k_lz_compress_marked, dim3(wave_window_grid(win, waves)),
-                       dim3(waves * 64), waves * per_wave, stream, base,
-                       scratch + half * chunk * granule,
-                       device_view(sizes + half * chunk), dev_words, dev_ranks,
-                       win, granule);
+    if (dictionary) {
+      const uint32_t per_wave = 3 * granule + kLzTableBytes;
+      const uint32_t waves = lzd_waves(per_wave);
+      hipLaunchKernelGGL(k_lzd_compress_marked,
+                         dim3(wave_window_grid(win, waves)), dim3(waves * 64),
+                         waves * per_wave, stream, base, dict,
+                         scratch + half * chunk * granule,
+                         device_view(sizes + half * chunk), dev_words,
+                         dev_ranks, win, granule);
+    } else {
+      const uint32_t per_wave = 2 * granule + kLzTableBytes;
+      const uint32_t waves = lz_waves(per_wave);
+      hipLaunchKernelGGL(k_lz_compress_marked,
+                         dim3(wave_window_grid(win, waves)), dim3(waves * 64),
+                         waves * per_wave, stream, base,
+                         scratch + half * chunk * granule,
+                         device_view(sizes + half * chunk), dev_words,
+                         dev_ranks, win, granule);
+    }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(packed[half], stream));
   }
@@ -504,9 +656,10 @@ struct LzStream : HalvesStream {
   }
 
   void decompress(const MarkedWindow& win, int half) {
-    const uint32_t per_wave = 2 * granule;
-    const uint32_t waves = lz_waves(per_wave);
-    hipLaunchKernelGGL(k_lz_decompress_marked,
+    const uint32_t per_wave = (dictionary ? 3 : 2) * granule;
+    const uint32_t waves = dictionary ? lzd_waves(per_wave) : lz_waves(per_wave);
+    hipLaunchKernelGGL(dictionary ? k_lzd_decompress_marked
+                                  : k_lz_decompress_marked,
                        dim3(wave_window_grid(win, waves)),
                        dim3(waves * 64), waves * per_wave, stream, base,
                        device_view(dense + half * chunk * granule),
@@ -573,7 +726,8 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
     status = source(data, sizes, win.first_rank, win.count);
     if (status == 0) {
       status = check_window(bitmap, data, sizes, win.first_rank, win.count,
-                            ls.granule, ls.offsets + half * ls.chunk, error);
+                            ls.granule, ls.dictionary,
+                            ls.offsets + half * ls.chunk, error);
     }
     if (status != kIoOk) break;
     ls.decompress(win, half);
@@ -585,21 +739,54 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
   if (gave_up(0) || gave_up(1)) {
     if (status == kIoOk) status = kIoFailed;
     if (error != nullptr && error->empty()) {
-      *error = "k_lz_decompress_marked gave up on a piece";
+      *error = ls.dictionary ? "k_lzd_decompress_marked gave up on a piece"
+                             : "k_lz_decompress_marked gave up on a piece";
     }
   }
   *unpacked = launched;
   return status;
 }
 
+// The marked granules of a range in ascending order, for the generic
+// HSLZD1 paths, whose chunks arrive in that order and need the index of
+// every granule to find its dictionary.
+struct MarkCursor {
+  const std::vector<uint64_t>& bitmap;
+  uint64_t n_granules;
+  uint64_t w = 0;
+  uint64_t word = 0;
+  bool loaded = false;
+
+  // The caller takes no more granules than the range has marks.
+  uint64_t next() {
+    for (;; ++w, loaded = false) {
+      if (!loaded) {
+        word = bitmap[w];
+        const uint64_t left = n_granules - w * 64;
+        if (left < 64) word &= (1ull << left) - 1;
+        loaded = true;
+      }
+      if (word != 0) break;
+    }
+    const uint64_t g = w * 64 + static_cast<uint64_t>(__builtin_ctzll(word));
+    word &= word - 1;
+    return g;
+  }
+};
+
 // Generic paths: bdev_pack_marked_sync / bdev_unpack_marked_sync cut the
-// chunks, the host codec does the rest.
-int compress_generic(Bdev* src, uint64_t offset, uint64_t length,
-                     uint32_t granule, const std::vector<uint64_t>& bitmap,
+// chunks, the host codec does the rest. With `base` (HSLZD1) the
+// dictionary of every granule is read from it, one granule (at most 16
+// KiB) per read.
+int compress_generic(Bdev* src, uint64_t offset, Bdev* base,
+                     uint64_t base_offset, uint64_t length, uint32_t granule,
+                     const std::vector<uint64_t>& bitmap,
                      uint64_t staging_bytes, const CompressSink& sink,
                      uint64_t* packed) {
   std::vector<uint8_t> pieces;
   std::vector<uint32_t> sizes;
+  std::vector<uint8_t> dict(base != nullptr ? granule : 0);
+  MarkCursor marks{bitmap, length / granule};
   return bdev_pack_marked_sync(
       src, offset, length, granule, bitmap, staging_bytes,
       [&](const uint8_t* data, uint64_t first_rank, uint64_t count) {
@@ -607,8 +794,17 @@ int compress_generic(Bdev* src, uint64_t offset, uint64_t length,
         sizes.resize(count);
         uint64_t at = 0;
         for (uint64_t i = 0; i < count; ++i) {
-          sizes[i] = lz_compress_granule(data + i * granule, granule,
-                                         pieces.data() + at);
+          if (base != nullptr) {
+            const int status = bdev_read_sync(
+                base, base_offset + marks.next() * granule, dict.data(),
+                granule);
+            if (status != kIoOk) return status;
+            sizes[i] = lz_dict_compress_granule(data + i * granule, dict.data(),
+                                                granule, pieces.data() + at);
+          } else {
+            sizes[i] = lz_compress_granule(data + i * granule, granule,
+                                           pieces.data() + at);
+          }
           at += lz_padded(sizes[i]);
         }
         return sink(pieces.data(), sizes.data(), first_rank, count);
@@ -619,11 +815,15 @@ int compress_generic(Bdev* src, uint64_t offset, uint64_t length,
 int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
                        uint32_t granule, const std::vector<uint64_t>& bitmap,
                        uint64_t staging_bytes,
-                       const DecompressSource& source, uint64_t* unpacked,
-                       std::string* error) {
+                       const DecompressSource& source, bool dictionary,
+                       uint64_t* unpacked, std::string* error) {
   std::vector<uint8_t> pieces;
   std::vector<uint32_t> sizes;
   std::vector<uint64_t> offsets;
+  std::vector<uint8_t> dict(dictionary ? granule : 0);
+  MarkCursor marks{bitmap, length / granule};
+  // A chunk is written after this returns, and no earlier chunk holds
+  // its granules: what is read here is the target's state before the call.
   return bdev_unpack_marked_sync(
       dst, offset, length, granule, bitmap, staging_bytes,
       [&](uint8_t* data, uint64_t first_rank, uint64_t count) {
@@ -633,11 +833,22 @@ int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
         int status = source(pieces.data(), sizes.data(), first_rank, count);
         if (status == 0) {
           status = check_window(bitmap, pieces.data(), sizes.data(), first_rank,
-                                count, granule, offsets.data(), error);
+                                count, granule, dictionary, offsets.data(),
+                                error);
         }
         for (uint64_t i = 0; status == kIoOk && i < count; ++i) {
-          lz_decompress_granule(pieces.data() + offsets[i], sizes[i], granule,
-                                data + i * granule);
+          if (!dictionary) {
+            lz_decompress_granule(pieces.data() + offsets[i], sizes[i], granule,
+                                  data + i * granule);
+            continue;
+          }
+          status = bdev_read_sync(dst, offset + marks.next() * granule,
+                                  dict.data(), granule);
+          if (status == kIoOk) {
+            lz_dict_decompress_granule(pieces.data() + offsets[i], sizes[i],
+                                       granule, dict.data(),
+                                       data + i * granule);
+          }
         }
         return status;
       },
@@ -687,8 +898,8 @@ int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
     if (status != kIoOk || plan.marked == 0) return status;
     const int device = granule_kernel_device(src, src);
     if (device < 0) {
-      return compress_generic(src, src_offset, length, granule, bitmap,
-                              staging_bytes, sink, packed);
+      return compress_generic(src, src_offset, nullptr, 0, length, granule,
+                              bitmap, staging_bytes, sink, packed);
     }
     LzStream ls(device, src, src_offset, granule, plan, true);
     return compress_gpu(ls, plan, sink, packed);
@@ -715,9 +926,81 @@ int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
     const int device = granule_kernel_device(dst, dst);
     if (device < 0) {
       return decompress_generic(dst, dst_offset, length, granule, bitmap,
-                                staging_bytes, source, unpacked, error);
+                                staging_bytes, source, false, unpacked, error);
     }
     LzStream ls(device, dst, dst_offset, granule, plan, false);
+    return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
+}
+
+int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
+                                   uint64_t base_offset, uint64_t length,
+                                   uint32_t granule,
+                                   const std::vector<uint64_t>& bitmap,
+                                   uint64_t staging_bytes,
+                                   const CompressSink& sink,
+                                   uint64_t* packed_out, std::string* error) {
+  uint64_t unused = 0;
+  uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
+  *packed = 0;
+  try {
+    if (!granule_ranges_ok(src, src_offset, base, base_offset, length, granule,
+                           &bitmap)) {
+      return kIoInvalid;
+    }
+    // Overlap is only possible within one backing store (validated
+    // ranges: the difference below cannot wrap).
+    const void* s_base = src->device_base();
+    const bool same_store =
+        src == base || (s_base != nullptr && s_base == base->device_base() &&
+                        src->gpu_device() == base->gpu_device());
+    if (same_store && std::max(src_offset, base_offset) -
+                              std::min(src_offset, base_offset) < length) {
+      if (error != nullptr) *error = "the volume and its base overlap";
+      return kIoInvalid;
+    }
+    MarkedPlan plan;
+    const int status = lz_plan(src, src_offset, length, granule, bitmap,
+                               staging_bytes, static_cast<bool>(sink), &plan,
+                               error);
+    if (status != kIoOk || plan.marked == 0) return status;
+    const int device = granule_kernel_device(src, base);
+    if (device < 0) {
+      return compress_generic(src, src_offset, base, base_offset, length,
+                              granule, bitmap, staging_bytes, sink, packed);
+    }
+    LzStream ls(device, src, src_offset, granule, plan, true, true,
+                static_cast<const uint8_t*>(base->device_base()) + base_offset);
+    return compress_gpu(ls, plan, sink, packed);
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
+}
+
+int bdev_dict_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
+                                     uint64_t length, uint32_t granule,
+                                     const std::vector<uint64_t>& bitmap,
+                                     uint64_t staging_bytes,
+                                     const DecompressSource& source,
+                                     uint64_t* unpacked_out,
+                                     std::string* error) {
+  uint64_t unused = 0;
+  uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
+  *unpacked = 0;
+  try {
+    MarkedPlan plan;
+    const int status = lz_plan(dst, dst_offset, length, granule, bitmap,
+                               staging_bytes, static_cast<bool>(source), &plan,
+                               error);
+    if (status != kIoOk || plan.marked == 0) return status;
+    const int device = granule_kernel_device(dst, dst);
+    if (device < 0) {
+      return decompress_generic(dst, dst_offset, length, granule, bitmap,
+                                staging_bytes, source, true, unpacked, error);
+    }
+    LzStream ls(device, dst, dst_offset, granule, plan, false, true);
     return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
   } catch (const std::exception&) {
     return kIoFailed;

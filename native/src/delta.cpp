@@ -35,6 +35,9 @@ const Format kDeltaLz = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
 const Format kDeltaXts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
                           {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
                           kDeltaVersionXts, "delta file"};
+const Format kDeltaDict = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
+                           {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
+                           kDeltaVersionDict, "delta file"};
 const Format kMap = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
                      {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
                      kFingerprintMapVersion, "fingerprint map"};
@@ -96,12 +99,14 @@ struct ParsedDelta {
 int parse_delta(const std::string& path, ParsedDelta* out,
                 std::string* error) {
   InFile& in = out->in;
-  int status = in.open(path, kDelta, error, &kDeltaLz, &kDeltaXts);
+  int status =
+      in.open(path, kDelta, error, {&kDeltaLz, &kDeltaXts, &kDeltaDict});
   if (status != kIoOk) return status;
   const Header& h = in.header;
   DeltaInfo& info = out->info;
   info.version = in.format().version;
-  info.compressed = info.version == kDeltaVersionLz;
+  info.dictionary = info.version == kDeltaVersionDict;
+  info.compressed = info.version == kDeltaVersionLz || info.dictionary;
   info.encrypted = info.version == kDeltaVersionXts;
   info.block_size = h.block_size;
   info.granule = h.granule;
@@ -111,8 +116,10 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   info.n_marked = get_u64(h.owned);
   info.file_bytes = in.file_bytes;
   // The spare words: version 1 none, version 2 both, version 3 the first.
-  if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz | kDeltaFlagXts)) != 0 ||
+  if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz | kDeltaFlagXts |
+                  kDeltaFlagDict)) != 0 ||
       ((h.word & kDeltaFlagLz) != 0) != info.compressed ||
+      ((h.word & kDeltaFlagDict) != 0) != info.dictionary ||
       ((h.word & kDeltaFlagXts) != 0) != info.encrypted ||
       (!info.compressed && get_u32(h.owned + 16) != 0) ||
       (!info.compressed && !info.encrypted && get_u32(h.owned + 12) != 0)) {
@@ -175,36 +182,44 @@ int parse_delta(const std::string& path, ParsedDelta* out,
 
 // The version-2 file: as write_delta, with the granules compressed
 // (bdev_compress_marked_sync) and record_area_bytes put into the header
-// once the records are out.
-int write_delta_lz(OutFile* out, Bdev* src,
+// once the records are out. With info->dictionary the version-4 file:
+// the same, compressed against `base` (bdev_dict_compress_marked_sync).
+int write_delta_lz(OutFile* out, Bdev* src, Bdev* base,
                    const std::vector<uint64_t>& bitmap, DeltaInfo* info,
                    std::string* error) {
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
   Header h = {info->block_size, info->granule,
-              (info->full ? kDeltaFlagFull : 0) | kDeltaFlagLz,
+              (info->full ? kDeltaFlagFull : 0) | kDeltaFlagLz |
+                  (info->dictionary ? kDeltaFlagDict : 0),
               info->volume_bytes, info->n_granules, {0}};
   put_u64(h.owned, info->n_marked);
   put_u32(h.owned + 8, crc32c_sw(0, raw.data(), raw.size()));
-  int status = out->begin(kDeltaLz, h, error);
+  int status = out->begin(info->dictionary ? kDeltaDict : kDeltaLz, h, error);
   if (status != kIoOk) return status;
   VarRecordWriter writer(out, info->granule, record_granules(info->granule),
                          info->n_marked);
   if (out->write(raw.data(), raw.size())) {  // else end() reports it
     uint64_t packed = 0;
     std::string why;
-    status = bdev_compress_marked_sync(
-        src, 0, info->volume_bytes, info->granule, bitmap, 0,
-        [&writer](const uint8_t* data, const uint32_t* sizes, uint64_t,
-                  uint64_t count) {
-          int added = kIoOk;
-          for (uint64_t i = 0; i < count && added == kIoOk; ++i) {
-            added = writer.add(data, sizes[i]);
-            data += lz_padded(sizes[i]);
-          }
-          return added;
-        },
-        &packed, &why);
+    const CompressSink sink = [&writer](const uint8_t* data,
+                                        const uint32_t* sizes, uint64_t,
+                                        uint64_t count) {
+      int added = kIoOk;
+      for (uint64_t i = 0; i < count && added == kIoOk; ++i) {
+        added = writer.add(data, sizes[i]);
+        data += lz_padded(sizes[i]);
+      }
+      return added;
+    };
+    status = info->dictionary
+                 ? bdev_dict_compress_marked_sync(src, 0, base, 0,
+                                                  info->volume_bytes,
+                                                  info->granule, bitmap, 0,
+                                                  sink, &packed, &why)
+                 : bdev_compress_marked_sync(src, 0, info->volume_bytes,
+                                             info->granule, bitmap, 0, sink,
+                                             &packed, &why);
     if (status != kIoOk || packed != info->n_marked || !writer.complete()) {
       if (why.empty()) {
         why = "reading the volume or writing " + out->tmp() + " failed";
@@ -224,10 +239,13 @@ int write_delta_lz(OutFile* out, Bdev* src,
 // synced. Fills info->file_bytes and info->stored_bytes. With `key`
 // (info->encrypted) the records hold what bdev_xts_pack_marked_sync
 // delivers and the header the key check value.
-int write_delta(OutFile* out, Bdev* src, const std::vector<uint64_t>& bitmap,
+int write_delta(OutFile* out, Bdev* src, Bdev* base,
+                const std::vector<uint64_t>& bitmap,
                 const std::vector<uint8_t>* key, DeltaInfo* info,
                 std::string* error) {
-  if (info->compressed) return write_delta_lz(out, src, bitmap, info, error);
+  if (info->compressed) {
+    return write_delta_lz(out, src, base, bitmap, info, error);
+  }
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
   Header h = {info->block_size, info->granule,
@@ -333,7 +351,7 @@ int choose_stored(const MapKind& want, const LoadedMap& stored,
 // bytes are kept.
 int load_map(const std::string& path, LoadedMap* out, std::string* error) {
   InFile in;
-  int status = in.open(path, kMap, error, &kMapBlake2s2);
+  int status = in.open(path, kMap, error, {&kMapBlake2s2});
   if (status != kIoOk) return status;
   const Header& h = in.header;
   FingerprintMapInfo& info = out->info;
@@ -508,8 +526,10 @@ int mark_all(Bdev* src, uint32_t granule, Marked* out, std::string* error) {
   return kIoOk;
 }
 
-// The record pass of a version-2 import. dry_run validates every piece
-// here; otherwise bdev_decompress_marked_sync does, before it decodes.
+// The record pass of a version-2 or version-4 import. dry_run validates
+// every piece here; otherwise bdev_decompress_marked_sync (version 4:
+// bdev_dict_decompress_marked_sync, whose dictionaries are the target's
+// granules) does, before it decodes.
 int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run, std::string* error) {
   const DeltaInfo& info = file->info;
   VarRecordReader reader(&file->in, file->records_offset, file->record_area,
@@ -526,7 +546,9 @@ int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run, std::string* error) {
         status = reader.next(&piece, &size, &why);
         std::string rule;
         if (status == kIoOk &&
-            !lz_validate_granule(piece, size, info.granule, &rule)) {
+            !(info.dictionary
+                  ? lz_dict_validate_granule(piece, size, info.granule, &rule)
+                  : lz_validate_granule(piece, size, info.granule, &rule))) {
           status = kIoInvalid;
           why = "granule " +
                 std::to_string(w * 64 +
@@ -538,20 +560,25 @@ int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run, std::string* error) {
     if (status != kIoOk) return fail(error, status, why);
   } else if (info.n_marked > 0) {
     uint64_t applied = 0;
-    status = bdev_decompress_marked_sync(
-        dst, 0, info.volume_bytes, info.granule, file->bitmap, 0,
-        [&](uint8_t* data, uint32_t* sizes, uint64_t, uint64_t count) {
-          for (uint64_t i = 0; i < count; ++i) {
-            const int got = reader.next(&piece, &size, &why);
-            if (got != kIoOk) return got;
-            sizes[i] = size;
-            memcpy(data, piece, size);
-            memset(data + size, 0, lz_padded(size) - size);
-            data += lz_padded(size);
-          }
-          return static_cast<int>(kIoOk);
-        },
-        &applied, &why);
+    const DecompressSource source = [&](uint8_t* data, uint32_t* sizes,
+                                        uint64_t, uint64_t count) {
+      for (uint64_t i = 0; i < count; ++i) {
+        const int got = reader.next(&piece, &size, &why);
+        if (got != kIoOk) return got;
+        sizes[i] = size;
+        memcpy(data, piece, size);
+        memset(data + size, 0, lz_padded(size) - size);
+        data += lz_padded(size);
+      }
+      return static_cast<int>(kIoOk);
+    };
+    status = info.dictionary
+                 ? bdev_dict_decompress_marked_sync(dst, 0, info.volume_bytes,
+                                                    info.granule, file->bitmap,
+                                                    0, source, &applied, &why)
+                 : bdev_decompress_marked_sync(dst, 0, info.volume_bytes,
+                                               info.granule, file->bitmap, 0,
+                                               source, &applied, &why);
     if (status != kIoOk) {
       if (why.empty()) why = "writing the target failed";
       return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
@@ -579,9 +606,13 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
                       DeltaInfo* stats, std::string* error, bool compress,
-                      const std::vector<uint8_t>* key) {
+                      const std::vector<uint8_t>* key, bool dictionary) {
   if (src == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
+  }
+  if (dictionary && (!compress || base == nullptr || key != nullptr)) {
+    return fail(error, kIoInvalid,
+                "dictionary needs compress and base (a clone), and no key");
   }
   if (key != nullptr && !xts_key_ok(key->data(), key->size())) {
     return fail(error, kIoInvalid,
@@ -635,10 +666,12 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
     return fail(error, kIoInvalid, "a key needs granule <= 16777216");
   }
   DeltaInfo info;
-  info.version = compress        ? kDeltaVersionLz
+  info.version = dictionary      ? kDeltaVersionDict
+                 : compress      ? kDeltaVersionLz
                  : key != nullptr ? kDeltaVersionXts
                                   : kDeltaVersion;
   info.compressed = compress;
+  info.dictionary = dictionary;
   info.encrypted = key != nullptr;
   info.block_size = static_cast<uint32_t>(src->block_size());
   info.granule = granule;
@@ -665,7 +698,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
   OutFile delta(path);
   OutFile map(map_out);
   FingerprintMapInfo map_info;
-  status = write_delta(&delta, src, marked.bitmap, key, &info, error);
+  status = write_delta(&delta, src, base, marked.bitmap, key, &info, error);
   if (status == kIoOk && !map_out.empty()) {
     status = write_map(&map, src->block_size(), granule, info.volume_bytes,
                        marked.fps, choice, &map_info, error);

@@ -1307,8 +1307,9 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         // Writes a volume, or with "base" its difference from an earlier
         // clone, to a delta file (HBM volumes leave through
         // k_pack_marked, one launch per staging window; with "compress"
-        // through k_lz_compress_marked and k_gather_var, with "key_file"
-        // through k_xts_pack_marked).
+        // through k_lz_compress_marked and k_gather_var, with "dictionary"
+        // too through k_lzd_compress_marked, with "key_file" through
+        // k_xts_pack_marked).
         const std::string name = p.get_string("name");
         BdevPtr src = manager.find(name);
         if (!src) not_found("bdev " + name);
@@ -1339,7 +1340,8 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         const int status =
             bdev_export_delta(src.get(), base.get(), path, granule,
                               p.get_bool("overwrite", false), &maps, &info,
-                              &why, p.get_bool("compress", false), key.ptr());
+                              &why, p.get_bool("compress", false), key.ptr(),
+                              p.get_bool("dictionary", false));
         if (status != kIoOk) throw delta_error("bdev_export_delta", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));
@@ -1351,6 +1353,7 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
           o["stored_bytes"] = Json(static_cast<int64_t>(info.stored_bytes));
         }
         if (info.encrypted) o["encrypted"] = Json(true);
+        if (info.dictionary) o["dictionary"] = Json(true);
         if (!maps.map_out.empty()) {
           o["map_bytes"] = Json(static_cast<int64_t>(maps.map_bytes));
         }

@@ -185,6 +185,7 @@ py::dict delta_info_to_dict(const DeltaInfo& info) {
     d["stored_bytes"] = info.stored_bytes;
   }
   if (info.encrypted) d["encrypted"] = true;
+  if (info.dictionary) d["dictionary"] = true;
   return d;
 }
 
@@ -707,7 +708,8 @@ PYBIND11_MODULE(_hipstore, m) {
                                 std::optional<std::string> map_out,
                                 bool compress, std::optional<py::bytes> key,
                                 std::optional<std::string> map_algorithm,
-                                std::optional<py::bytes> map_key) {
+                                std::optional<py::bytes> map_key,
+                                bool dictionary) {
     DeltaInfo info;
     DeltaMaps maps;
     const KeyArg key_arg(key);
@@ -718,7 +720,7 @@ PYBIND11_MODULE(_hipstore, m) {
     delta_call("bdev_export_delta", [&](std::string* error) {
       return bdev_export_delta(src.get(), base ? base->get() : nullptr, path,
                                granule.value_or(0), overwrite, &maps, &info,
-                               error, compress, key_arg.ptr());
+                               error, compress, key_arg.ptr(), dictionary);
     });
     py::dict d = delta_info_to_dict(info);
     if (!maps.map_out.empty()) d["map_bytes"] = maps.map_bytes;
@@ -728,13 +730,16 @@ PYBIND11_MODULE(_hipstore, m) {
      py::arg("base_map") = py::none(), py::arg("map_out") = py::none(),
      py::arg("compress") = false, py::arg("key") = py::none(),
      py::arg("map_algorithm") = py::none(), py::arg("map_key") = py::none(),
+     py::arg("dictionary") = false,
      "Write the granules of src that differ from base, or from the state "
      "recorded in the fingerprint map base_map (every granule without "
      "either), to a hipstore delta file; map_out also writes the "
      "fingerprint map of src; compress writes a version-2 file of HSLZ1 "
      "pieces, key (64 bytes) a version-3 file of HSXTS1 ciphertext; "
      "map_algorithm \"blake2s\" and map_key (32 bytes) make map_out an "
-     "HSFP2 map (base_map decides by itself)");
+     "HSFP2 map (base_map decides by itself); dictionary (with compress "
+     "and base) a version-4 file of HSLZD1 pieces, every granule "
+     "compressed against the same granule of base");
 
   m.def("xts_encrypt_units", [](py::bytes data, uint32_t granule,
                                 py::bytes key, uint64_t first_unit) {
@@ -845,80 +850,121 @@ PYBIND11_MODULE(_hipstore, m) {
      "marked in `bitmap` (k_xts_unpack_marked for HBM bdevs); returns the "
      "number written");
 
-  m.def("lz_compress_granule", [](py::bytes data) {
+  m.def("lz_compress_granule", [](py::bytes data,
+                                  std::optional<py::bytes> dictionary) {
     const std::string in = data;
     if (!lz_granule_ok(in.size())) {
       throw std::invalid_argument(
           "lz_compress_granule: 512 <= length <= 16384, a multiple of 16");
     }
     std::string out(in.size(), '\0');
-    const uint32_t size = lz_compress_granule(
-        reinterpret_cast<const uint8_t*>(in.data()),
-        static_cast<uint32_t>(in.size()), reinterpret_cast<uint8_t*>(&out[0]));
+    uint32_t size = 0;
+    if (dictionary) {
+      const std::string dict = *dictionary;
+      if (dict.size() != in.size()) {
+        throw std::invalid_argument(
+            "lz_compress_granule: the dictionary must be as long as the data");
+      }
+      size = lz_dict_compress_granule(
+          reinterpret_cast<const uint8_t*>(in.data()),
+          reinterpret_cast<const uint8_t*>(dict.data()),
+          static_cast<uint32_t>(in.size()),
+          reinterpret_cast<uint8_t*>(&out[0]));
+    } else {
+      size = lz_compress_granule(reinterpret_cast<const uint8_t*>(in.data()),
+                                 static_cast<uint32_t>(in.size()),
+                                 reinterpret_cast<uint8_t*>(&out[0]));
+    }
     out.resize(size);
     return py::bytes(out);
-  }, py::arg("data"),
+  }, py::arg("data"), py::arg("dictionary") = py::none(),
      "The stored form of one granule: an LZ4 block, or the granule itself "
      "when that would not be smaller (host codec, the byte model of "
-     "k_lz_compress_marked)");
+     "k_lz_compress_marked); with `dictionary` (as long as the data) the "
+     "HSLZD1 form, the byte model of k_lzd_compress_marked");
 
-  m.def("lz_decompress_granule", [](py::bytes piece, uint32_t granule) {
+  m.def("lz_decompress_granule", [](py::bytes piece, uint32_t granule,
+                                    std::optional<py::bytes> dictionary) {
     const std::string in = piece;
     std::string out(lz_granule_ok(granule) ? granule : 0, '\0');
     std::string why;
-    if (!lz_decompress_granule(reinterpret_cast<const uint8_t*>(in.data()),
-                               in.size(), granule,
-                               reinterpret_cast<uint8_t*>(&out[0]), &why)) {
-      throw std::invalid_argument("lz_decompress_granule: " + why);
+    bool ok = false;
+    if (dictionary) {
+      const std::string dict = *dictionary;
+      if (dict.size() != out.size()) {
+        throw std::invalid_argument(
+            "lz_decompress_granule: the dictionary must be one granule");
+      }
+      ok = lz_dict_decompress_granule(
+          reinterpret_cast<const uint8_t*>(in.data()), in.size(), granule,
+          reinterpret_cast<const uint8_t*>(dict.data()),
+          reinterpret_cast<uint8_t*>(&out[0]), &why);
+    } else {
+      ok = lz_decompress_granule(reinterpret_cast<const uint8_t*>(in.data()),
+                                 in.size(), granule,
+                                 reinterpret_cast<uint8_t*>(&out[0]), &why);
     }
+    if (!ok) throw std::invalid_argument("lz_decompress_granule: " + why);
     return py::bytes(out);
-  }, py::arg("piece"), py::arg("granule"),
-     "Decode one stored piece (host codec); ValueError for a malformed one");
+  }, py::arg("piece"), py::arg("granule"), py::arg("dictionary") = py::none(),
+     "Decode one stored piece (host codec), an HSLZD1 piece with its "
+     "`dictionary`; ValueError for a malformed one");
 
-  m.def("lz_validate_granule", [](py::bytes piece, uint32_t granule) {
+  m.def("lz_validate_granule", [](py::bytes piece, uint32_t granule,
+                                  bool dictionary) {
     const std::string in = piece;
-    return lz_validate_granule(reinterpret_cast<const uint8_t*>(in.data()),
-                               in.size(), granule);
-  }, py::arg("piece"), py::arg("granule"),
-     "True when a stored piece passes the token walk import runs");
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(in.data());
+    return dictionary ? lz_dict_validate_granule(p, in.size(), granule)
+                      : lz_validate_granule(p, in.size(), granule);
+  }, py::arg("piece"), py::arg("granule"), py::arg("dictionary") = false,
+     "True when a stored piece passes the token walk import runs; "
+     "`dictionary` selects the HSLZD1 walk, which needs no dictionary bytes");
 
   m.def("bdev_compress_marked", [](BdevPtr src, py::bytes bitmap,
                                    uint32_t granule, uint64_t src_offset,
                                    std::optional<uint64_t> length,
-                                   uint64_t staging_bytes) {
+                                   uint64_t staging_bytes,
+                                   std::optional<BdevPtr> base,
+                                   uint64_t base_offset) {
     const std::string raw = bitmap;
     const uint64_t len = marked_range("bdev_compress_marked", *src, src_offset,
                                       length, granule, raw);
     const std::vector<uint64_t> words = bitmap_words(raw);
     std::vector<uint32_t> sizes;
     std::string out;
+    const CompressSink sink = [&](const uint8_t* data, const uint32_t* window,
+                                  uint64_t, uint64_t count) {
+      for (uint64_t i = 0; i < count; ++i) {
+        out.append(reinterpret_cast<const char*>(data), window[i]);
+        data += lz_padded(window[i]);
+      }
+      sizes.insert(sizes.end(), window, window + count);
+      return 0;
+    };
     delta_call("bdev_compress_marked", [&](std::string* error) {
-      return bdev_compress_marked_sync(
-          src.get(), src_offset, len, granule, words, staging_bytes,
-          [&](const uint8_t* data, const uint32_t* window, uint64_t,
-              uint64_t count) {
-            for (uint64_t i = 0; i < count; ++i) {
-              out.append(reinterpret_cast<const char*>(data), window[i]);
-              data += lz_padded(window[i]);
-            }
-            sizes.insert(sizes.end(), window, window + count);
-            return 0;
-          },
-          nullptr, error);
+      return base ? bdev_dict_compress_marked_sync(
+                        src.get(), src_offset, base->get(), base_offset, len,
+                        granule, words, staging_bytes, sink, nullptr, error)
+                  : bdev_compress_marked_sync(src.get(), src_offset, len,
+                                              granule, words, staging_bytes,
+                                              sink, nullptr, error);
     });
     return py::make_tuple(sizes, py::bytes(out));
   }, py::arg("src"), py::arg("bitmap"), py::arg("granule"),
      py::arg("src_offset") = 0, py::arg("length") = py::none(),
-     py::arg("staging_bytes") = 0,
+     py::arg("staging_bytes") = 0, py::arg("base") = py::none(),
+     py::arg("base_offset") = 0,
      "Compress the granules marked in `bitmap`, ascending (on-GPU for HBM "
-     "bdevs): (stored sizes, the pieces back to back)");
+     "bdevs): (stored sizes, the pieces back to back). With `base`, every "
+     "granule is compressed against the same granule of the range of "
+     "`base` at base_offset (HSLZD1)");
 
   m.def("bdev_decompress_marked", [](BdevPtr dst, py::bytes bitmap,
                                      uint32_t granule,
                                      std::vector<uint32_t> sizes,
                                      py::bytes data, uint64_t dst_offset,
                                      std::optional<uint64_t> length,
-                                     uint64_t staging_bytes) {
+                                     uint64_t staging_bytes, bool dictionary) {
     const std::string raw = bitmap;
     const uint64_t len = marked_range("bdev_decompress_marked", *dst,
                                       dst_offset, length, granule, raw);
@@ -934,31 +980,37 @@ PYBIND11_MODULE(_hipstore, m) {
           "bdev_decompress_marked: sizes do not add up to the data length");
     }
     uint64_t unpacked = 0;
+    const DecompressSource source = [&](uint8_t* out, uint32_t* window,
+                                        uint64_t first_rank, uint64_t count) {
+      if (first_rank + count > sizes.size()) return static_cast<int>(kIoInvalid);
+      for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t size = sizes[first_rank + i];
+        window[i] = size;
+        if (size == 0 || size > granule) continue;  // refused after us
+        memcpy(out, pieces.data() + starts[first_rank + i], size);
+        memset(out + size, 0, lz_padded(size) - size);
+        out += lz_padded(size);
+      }
+      return 0;
+    };
     delta_call("bdev_decompress_marked", [&](std::string* error) {
-      return bdev_decompress_marked_sync(
-          dst.get(), dst_offset, len, granule, words, staging_bytes,
-          [&](uint8_t* out, uint32_t* window, uint64_t first_rank,
-              uint64_t count) {
-            if (first_rank + count > sizes.size()) return static_cast<int>(kIoInvalid);
-            for (uint64_t i = 0; i < count; ++i) {
-              const uint32_t size = sizes[first_rank + i];
-              window[i] = size;
-              if (size == 0 || size > granule) continue;  // refused after us
-              memcpy(out, pieces.data() + starts[first_rank + i], size);
-              memset(out + size, 0, lz_padded(size) - size);
-              out += lz_padded(size);
-            }
-            return 0;
-          },
-          &unpacked, error);
+      return dictionary
+                 ? bdev_dict_decompress_marked_sync(dst.get(), dst_offset, len,
+                                                    granule, words,
+                                                    staging_bytes, source,
+                                                    &unpacked, error)
+                 : bdev_decompress_marked_sync(dst.get(), dst_offset, len,
+                                               granule, words, staging_bytes,
+                                               source, &unpacked, error);
     });
     return unpacked;
   }, py::arg("dst"), py::arg("bitmap"), py::arg("granule"), py::arg("sizes"),
      py::arg("data"), py::arg("dst_offset") = 0, py::arg("length") = py::none(),
-     py::arg("staging_bytes") = 0,
+     py::arg("staging_bytes") = 0, py::arg("dictionary") = false,
      "Decode the pieces of bdev_compress_marked into the granules marked in "
      "`bitmap`; every piece is validated on the host first. Returns the "
-     "number written");
+     "number written. `dictionary`: the pieces are HSLZD1 and the "
+     "dictionary of a granule is what `dst` holds there before the call");
 
   m.def("xts_marked_probe", [](BdevPtr bdev, py::bytes bitmap,
                                uint32_t granule, py::bytes key, bool unpack,

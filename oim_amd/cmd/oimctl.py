@@ -86,6 +86,10 @@ def main(argv=None) -> int:
             cmd.add_argument("--compress", action="store_true",
                              help="store every granule LZ-compressed "
                              "(restore reads either kind of file)")
+            cmd.add_argument("--dictionary", action="store_true",
+                             help="with --compress and --base: compress "
+                             "every granule against the base's (restore "
+                             "onto a volume at the base state, once)")
         if name in ("checkpoint", "restore"):
             cmd.add_argument("--key-file", default="",
                              help="file of 64 raw bytes on the data-path "
@@ -189,7 +193,8 @@ def main(argv=None) -> int:
                         base_map=args.base_map, map_out=args.map_out,
                         compress=args.compress, key_file=args.key_file,
                         map_algorithm=args.map_algorithm,
-                        map_key_file=args.map_key_file),
+                        map_key_file=args.map_key_file,
+                        dictionary=args.dictionary),
                     metadata=metadata, timeout=600)
                 print(f"checkpointed {args.volume} -> {args.path}: "
                       f"{reply.saved} of {reply.granules} granules, "

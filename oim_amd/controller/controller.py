@@ -421,7 +421,8 @@ class Controller(spec.ControllerServicer):
                         compress=request.compress,
                         key_file=request.key_file or None,
                         map_algorithm=request.map_algorithm or None,
-                        map_key_file=request.map_key_file or None)
+                        map_key_file=request.map_key_file or None,
+                        dictionary=request.dictionary)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.CheckpointMallocBDevReply(

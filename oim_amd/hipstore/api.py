@@ -349,7 +349,8 @@ def bdev_export_delta(client: Client, name: str, path: str,
                       compress: bool = False,
                       key_file: Optional[str] = None,
                       map_algorithm: Optional[str] = None,
-                      map_key_file: Optional[str] = None) -> Dict:
+                      map_key_file: Optional[str] = None,
+                      dictionary: bool = False) -> Dict:
     """Checkpoint a volume to a delta file: every granule, or with
     `base` (an earlier clone) or `base_map` (the fingerprint map written
     with an earlier checkpoint; no clone needed) only the granules that
@@ -364,7 +365,11 @@ def bdev_export_delta(client: Client, name: str, path: str,
     fingerprints (HSFP2; default "hsfp1"), `map_key_file` (a file of
     exactly 32 raw bytes that the daemon reads) a keyed one, which
     authenticates the volume; with `base_map` that map decides and a
-    keyed one needs its key.
+    keyed one needs its key. `dictionary` (only with `compress` and
+    `base`, never with `key_file`) compresses every granule against the
+    same granule of `base` (a version-4 file): an in-place edit of a
+    granule then costs a few dozen bytes whatever the content. Such a
+    file must be imported onto a volume that is at the base state, once.
 
     Returns {granule, granules, saved, file_bytes, full}, with map_out
     also map_bytes and with compress stored_bytes (the bytes the granules
@@ -385,6 +390,8 @@ def bdev_export_delta(client: Client, name: str, path: str,
         params["compress"] = True
     if key_file is not None:
         params["key_file"] = key_file
+    if dictionary:
+        params["dictionary"] = True
     _map_params(params, map_algorithm, map_key_file)
     return client.invoke("bdev_export_delta", params)
 

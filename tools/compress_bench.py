@@ -13,7 +13,17 @@ compress, import and import of the compressed file, each timed around
 the Python call (the file is on --dir, a tmpfs). Prints one JSON line
 per content with medians, min-max, GB/s of volume bytes and the achieved
 ratio. --no-compress runs the uncompressed half only, which is all a
-build without the feature has. Needs a GPU: there is no fallback."""
+build without the feature has. Needs a GPU: there is no fallback.
+
+    python tools/compress_bench.py --dictionary [--changed 0.01] ...
+
+measures an incremental instead: a base volume (text or random; sparse
+is skipped), a live volume that differs from it in `--changed` of the
+granules by a 64-byte in-place edit, and per round an export against the
+base as a version-1, a version-2 (compress) and a version-4 (compress,
+dictionary) file, each imported onto a third volume that was put back to
+the base state first (untimed). One JSON line per content with the
+times, the file sizes and the stored ratios of the changed granules."""
 import argparse
 import json
 import os
@@ -52,6 +62,65 @@ def summary(samples, nbytes):
             "gb_per_s": round(nbytes / med / 1e9, 3)}
 
 
+def incremental(args, length, live, back):
+    """The --dictionary half: see the module docstring."""
+    block = 512
+    base = hs.create_hbm_bdev("lzbench-base", block, length // block,
+                              device=args.device)
+    path = os.path.join(args.dir, f"lzbench-{os.getpid()}.delta")
+    undo = path + ".undo"
+    n = length // args.granule
+    modes = {"v1": {}, "v2": {"compress": True},
+             "v4": {"compress": True, "dictionary": True}}
+    for kind in args.contents:
+        if kind == "sparse":
+            continue
+        rng = np.random.default_rng(20264)
+        off = 0
+        for chunk in content_chunks(kind, length, rng):
+            for bdev in (base, live, back):
+                bdev.write(off, chunk)
+            off += len(chunk)
+        changed = rng.choice(n, size=max(1, int(n * args.changed)),
+                             replace=False)
+        for g in changed:  # 64 bytes in place; 512-byte blocks
+            at = int(g) * args.granule + args.granule // 2
+            sector = bytearray(live.read(at, block))
+            sector[:64] = rng.integers(0, 256, 64, dtype=np.uint8).tobytes()
+            live.write(at, bytes(sector))
+        hs.bdev_export_delta(base, undo, base=live, granule=args.granule,
+                             overwrite=True)
+        out = {"content": kind, "volume_bytes": length, "granule": args.granule,
+               "changed_granules": len(changed)}
+        samples = {(what, m): [] for what in ("export", "import")
+                   for m in modes}
+        for run in range(args.runs + 1):  # run 0 warms up
+            for m, kwargs in modes.items():
+                hs.bdev_import_delta(back, undo)  # back to the base state
+                t0 = time.perf_counter()
+                info = hs.bdev_export_delta(live, path, base=base,
+                                            granule=args.granule,
+                                            overwrite=True, **kwargs)
+                t1 = time.perf_counter()
+                hs.bdev_import_delta(back, path)
+                t2 = time.perf_counter()
+                if run > 0:
+                    samples[("export", m)].append(t1 - t0)
+                    samples[("import", m)].append(t2 - t1)
+                out["file_bytes_" + m] = info["file_bytes"]
+                if "stored_bytes" in info:
+                    out["ratio_" + m] = round(
+                        len(changed) * args.granule / info["stored_bytes"], 2)
+                if hs.bdev_diff(live, back,
+                                granule=args.granule)["mismatched"] != 0:
+                    sys.exit(f"compress_bench: {kind} {m}: restore differs")
+        for (what, m), values in samples.items():
+            out[f"{what}_{m}"] = summary(values, length)
+        os.unlink(path)
+        os.unlink(undo)
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--gib", type=float, default=8.0, help="volume size")
@@ -62,6 +131,10 @@ def main():
     ap.add_argument("--dir", default="/dev/shm", help="where exports go")
     ap.add_argument("--no-compress", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--dictionary", action="store_true",
+                    help="measure an incremental as version 1, 2 and 4")
+    ap.add_argument("--changed", type=float, default=0.01,
+                    help="with --dictionary: share of granules edited")
     args = ap.parse_args()
     if not hs.gpu_available():
         sys.exit("compress_bench: no HIP device (no fallback)")
@@ -72,6 +145,8 @@ def main():
                               device=args.device)
     back = hs.create_hbm_bdev("lzbench-back", block, length // block,
                               device=args.device)
+    if args.dictionary:
+        return incremental(args, length, live, back)
     path = os.path.join(args.dir, f"lzbench-{os.getpid()}.delta")
     modes = [False] if args.no_compress else [False, True]
 
