@@ -19,7 +19,7 @@ LDLIBS := -L$(ROCM)/lib -lrccl
 B := native/build
 HDRS := $(wildcard native/include/hipstore/*.h)
 HIP_HDRS := $(HDRS) native/src/gpu_internal.h native/src/marked_internal.h \
-            native/src/blake2s_internal.h
+            native/src/blake2s_internal.h native/src/crypt_internal.h
 
 CORE_OBJS := $(B)/json.o $(B)/bdev.o $(B)/crc32c.o $(B)/rpc_server.o \
              $(B)/methods.o $(B)/nbd.o $(B)/ublk.o $(B)/composite.o $(B)/vhost.o $(B)/vhost_master.o \
@@ -142,6 +142,16 @@ $(B)/crypt_test_asan: $(CRYPT_TEST_SRCS) $(HDRS) | $(B)
 .PHONY: crypt-test
 crypt-test: $(B)/crypt_test_asan
 	$(B)/crypt_test_asan
+
+# The same for the HSXTS2 host codec (ciphertext stealing).
+CRYPT_CTS_TEST_SRCS := tests/native/crypt_cts_test.cpp native/src/crypt.cpp
+
+$(B)/crypt_cts_test_asan: $(CRYPT_CTS_TEST_SRCS) $(HDRS) | $(B)
+	$(HIPCC) $(CXXFLAGS) -O1 -g -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(CRYPT_CTS_TEST_SRCS) -o $@
+
+.PHONY: crypt-cts-test
+crypt-cts-test: $(B)/crypt_cts_test_asan
+	$(B)/crypt_cts_test_asan
 
 # Stand-alone check of the HSFP2 host code (the RFC 7693 vector, the
 # per-granule BLAKE2s hasher cut at every 16-byte boundary) under

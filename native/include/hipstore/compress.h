@@ -134,7 +134,9 @@ int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               const std::vector<uint64_t>& bitmap,
                               uint64_t staging_bytes, const CompressSink& sink,
                               uint64_t* packed = nullptr,
-                              std::string* error = nullptr);
+                              std::string* error = nullptr,
+                              const uint8_t* key = nullptr, size_t key_len = 0,
+                              uint64_t first_unit = 0);
 
 // The inverse: source(data, sizes, first_rank, count) fills the stored
 // sizes and the pieces of the next chunk in the layout above (`data` has
@@ -154,7 +156,30 @@ int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 uint64_t staging_bytes,
                                 const DecompressSource& source,
                                 uint64_t* unpacked = nullptr,
-                                std::string* error = nullptr);
+                                std::string* error = nullptr,
+                                const uint8_t* key = nullptr,
+                                size_t key_len = 0, uint64_t first_unit = 0);
+
+// Keyed calls. All four calls take an optional key (the 64 bytes of
+// crypt.h) and a first unit number: every piece is then one HSXTS2 unit
+// whose number is first_unit + the granule's index in the range, and only
+// ciphertext reaches the sink or comes from the source. `sizes` stay the
+// true stored sizes; piece i sits at the sum of lz_padded(max(sizes[j],
+// 16)) over j < i, because a piece shorter than a cipher block is stored
+// as one zero-padded block. kIoInvalid unless xts_key_ok and first_unit +
+// the range's granules stays below 2^64-1, before anything runs.
+//   compress, HBM: k_xts_var takes k_gather_var's place and encrypts the
+//     pieces on their way from device scratch to pinned memory, so no
+//     plaintext crosses PCIe or sits in pinned host memory.
+//   decompress, HBM: the host sees only ciphertext and checks the sizes
+//     alone. k_xts_var decrypts the window into device scratch and the
+//     decode kernels run in strict mode, where they accept exactly the
+//     pieces lz_validate_granule (lz_dict_validate_granule) accepts; a
+//     piece they refuse is kIoInvalid, `error` names the granule and the
+//     granule is left alone.
+//   every other bdev: xts_encrypt_var / xts_decrypt_var on the host, then
+//     the host validators as without a key. Both paths hand over the same
+//     chunks and bytes and refuse the same pieces.
 
 // bdev_compress_marked_sync with HSLZD1: granule g of the range of `src`
 // is compressed against granule g of the range of `base` (same block
@@ -171,7 +196,10 @@ int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
                                    uint64_t staging_bytes,
                                    const CompressSink& sink,
                                    uint64_t* packed = nullptr,
-                                   std::string* error = nullptr);
+                                   std::string* error = nullptr,
+                                   const uint8_t* key = nullptr,
+                                   size_t key_len = 0,
+                                   uint64_t first_unit = 0);
 
 // bdev_decompress_marked_sync with HSLZD1: the dictionary of a granule is
 // what the target holds there when the call reaches it, so the target
@@ -184,6 +212,9 @@ int bdev_dict_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                      uint64_t staging_bytes,
                                      const DecompressSource& source,
                                      uint64_t* unpacked = nullptr,
-                                     std::string* error = nullptr);
+                                     std::string* error = nullptr,
+                                     const uint8_t* key = nullptr,
+                                     size_t key_len = 0,
+                                     uint64_t first_unit = 0);
 
 }  // namespace hipstore

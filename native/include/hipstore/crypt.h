@@ -21,8 +21,23 @@
 //              known plaintext.
 // With G = 512 this is the aes-xts-plain64 layout.
 //
-// The host codec below is the byte model of k_xts_pack_marked and
-// k_xts_unpack_marked (crypt_ops.hip) and a different algorithm on
+// "HSXTS2" is HSXTS1 with the data unit generalised to any n bytes, 16 <=
+// n <= 2^24: IEEE 1619 ciphertext stealing. It encrypts the compressed
+// pieces of version-5 delta files (delta.h). Key, unit number, tweak, kcv
+// and alpha are unchanged. With n = 16 * m + b, 0 <= b < 16:
+//   b == 0     exactly HSXTS1.
+//   otherwise  blocks 0 .. m-2 as in HSXTS1; CC = E(P_{m-1}, T_{m-1}); the
+//              stored tail C_m is the first b bytes of CC; PP = P_m (b
+//              bytes) || CC[b..16); the stored C_{m-1} = E(PP, T_m).
+//              Decryption: C_{m-1} under T_m gives PP, then C_m ||
+//              PP[b..16) under T_{m-1} gives P_{m-1}.
+// The stored length equals the plaintext length. A piece shorter than 16
+// bytes (a dictionary piece of a small granule) is zero-padded to one
+// block and stored as 16 bytes; its recorded size stays the true one and
+// the reader ignores the pad.
+//
+// The host codec below is the byte model of k_xts_pack_marked,
+// k_xts_unpack_marked and k_xts_var (crypt_ops.hip) and a different algorithm on
 // purpose: byte-wise S-box, ShiftRows and xtime MixColumns, the straight
 // inverse cipher, the tweak doubled block by block. The kernels use
 // T-tables, the equivalent inverse cipher and log-step tweaks.
@@ -77,6 +92,13 @@ void xts_encrypt_unit(const XtsSchedules& keys, uint64_t unit,
                       const uint8_t* in, uint8_t* out, uint32_t bytes);
 void xts_decrypt_unit(const XtsSchedules& keys, uint64_t unit,
                       const uint8_t* in, uint8_t* out, uint32_t bytes);
+
+// HSXTS2: one data unit of any `bytes` >= 16; in == out is fine. A
+// multiple of 16 gives what the unit functions give.
+void xts_encrypt_var(const XtsSchedules& keys, uint64_t unit,
+                     const uint8_t* in, uint8_t* out, uint32_t bytes);
+void xts_decrypt_var(const XtsSchedules& keys, uint64_t unit,
+                     const uint8_t* in, uint8_t* out, uint32_t bytes);
 
 // xts_key_ok(key) required.
 uint32_t xts_kcv(const uint8_t key[kXtsKeyBytes]);

@@ -44,8 +44,9 @@
 // Record CRCs, the bitmap CRC and the exact-length rule are computed over
 // the file as stored, so the structural pass and a dry run need no key.
 // There is no authentication (a CRC is not a MAC), and a key together
-// with `compress` is refused: compress-then-encrypt needs padding or
-// ciphertext stealing.
+// with `compress` is refused unless `cts` asks for version 5:
+// compress-then-encrypt needs ciphertext stealing, which older readers
+// do not have.
 //
 // "hipstore delta file, version 4" holds the granules of an incremental
 // compressed against the base (HSLZD1, compress.h: the dictionary of a
@@ -67,6 +68,32 @@
 // at the base state it decodes memory-safely into wrong data. A map_out
 // map of the export plus bdev_verify_fingerprints after the import is the
 // check.
+//
+// "hipstore delta file, version 5" holds the granules compressed and then
+// encrypted (HSLZ1 or HSLZD1 pieces, each one HSXTS2 data unit, crypt.h:
+// XTS with ciphertext stealing; the unit number is the granule's index in
+// the volume) and is what an export with `compress`, a key and `cts`
+// writes. The layout is version 2's with
+//   - version = 5 and flags bit 1 (kDeltaFlagLz) and bit 2 (kDeltaFlagXts)
+//     both set; version 5 if and only if both; bit 3 (kDeltaFlagDict) says
+//     whether the pieces are HSLZD1, with version 4's rules for the base
+//   - a 16-byte key block directly after the bitmap: "HSKC", u32
+//     xts_kcv(key), u32 0, u32 crc32c of those 12 bytes; record_area_bytes
+//     does not count it, and the exact file length still follows from the
+//     header
+//   - in a record's payload a piece occupies max(size, 16) bytes: a piece
+//     shorter than one cipher block is stored as one zero-padded encrypted
+//     block. The sizes stay the true stored sizes, 1 .. granule.
+// Record CRCs, the bitmap CRC, the range check of the sizes and the
+// exact-length rule are computed over the file as stored, so the
+// structural pass and a dry run need no key; a wrong key is refused by
+// kcv before the target is touched. The pieces can be validated only
+// after decryption: on an HBM target that happens on the GPU, in the
+// strict decode (compress.h), otherwise on the host; both refuse the same
+// files, name the granule and leave it unwritten. Stored sizes are in the
+// clear, so the file shows how compressible every granule is; equal
+// granule index, key and plaintext give equal ciphertext across files, as
+// in version 3; and there is still no authentication.
 
 #pragma once
 
@@ -86,6 +113,7 @@ constexpr uint32_t kDeltaFlagLz = 2;
 constexpr uint32_t kDeltaFlagXts = 4;
 constexpr uint32_t kDeltaVersionDict = 4;
 constexpr uint32_t kDeltaFlagDict = 8;
+constexpr uint32_t kDeltaVersionCts = 5;
 constexpr uint64_t kDeltaHeaderBytes = 64;
 constexpr uint64_t kDeltaTrailerBytes = 16;
 constexpr uint64_t kDeltaRecordBytes = 1ull << 20;
@@ -99,12 +127,12 @@ struct DeltaInfo {
   uint64_t n_granules = 0;
   uint64_t n_marked = 0;  // granules in the file (saved / applied)
   uint64_t file_bytes = 0;
-  bool compressed = false;  // version 2
+  bool compressed = false;  // versions 2, 4 and 5
   // Bytes the granules take in the file: n_marked * granule, or the sum
   // of the stored sizes of a compressed file.
   uint64_t stored_bytes = 0;
-  bool encrypted = false;  // version 3
-  bool dictionary = false;  // version 4 (then also compressed)
+  bool encrypted = false;  // versions 3 and 5
+  bool dictionary = false;  // version 4, or 5 with bit 3 (then also compressed)
 };
 
 // Every call returns an IoStatus and, on failure, a one-line reason in
@@ -131,11 +159,12 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
 // dry_run runs every check and writes nothing. A claimed target is
 // refused.
 //
-// `key` (the 64 bytes of crypt.h) is required for a version-3 file and
-// kIoInvalid for any other; a key whose xts_kcv differs from the header's
-// is kIoInvalid before the target is touched. dry_run of a version-3
-// file works without a key (structure and CRCs, so a file can be vetted
-// where the key is not) and with one also checks the kcv.
+// `key` (the 64 bytes of crypt.h) is required for a version-3 or
+// version-5 file and kIoInvalid for any other; a key whose xts_kcv differs
+// from the file's is kIoInvalid before the target is touched. dry_run of
+// such a file works without a key (structure and CRCs, so a file can be
+// vetted where the key is not) and with one also checks the kcv and, for
+// version 5, decrypts and validates every piece.
 int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
                       DeltaInfo* stats, std::string* error,
                       const std::vector<uint8_t>* key = nullptr);
@@ -267,6 +296,11 @@ int bdev_verify_fingerprints(Bdev* bdev, const std::string& path,
 // `base` (a full export or `base_map`, which has no base bytes) or
 // together with `key` it is kIoInvalid before anything is written.
 //
+// `cts` writes a version-5 file: `compress` and `key` together, with or
+// without `dictionary`. It is opt-in because older readers cannot read
+// version 5: without it `key` with `compress` and `dictionary` with `key`
+// stay refused. `cts` without both `key` and `compress` is kIoInvalid.
+//
 // `kind` says which fingerprints the maps hold. With `base_map`, the pass
 // and `map_out` take the base map's algorithm and the rules of
 // bdev_verify_fingerprints apply; without, `map_out` is written as `kind`
@@ -283,6 +317,6 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       DeltaInfo* stats, std::string* error,
                       bool compress = false,
                       const std::vector<uint8_t>* key = nullptr,
-                      bool dictionary = false);
+                      bool dictionary = false, bool cts = false);
 
 }  // namespace hipstore

@@ -171,9 +171,10 @@ int RecordReader::next_record(std::string* error) {
 
 VarRecordReader::VarRecordReader(const InFile* in, uint64_t offset,
                                  uint64_t area, uint64_t max_unit,
-                                 uint64_t per_record, uint64_t total)
+                                 uint64_t per_record, uint64_t total,
+                                 uint64_t min_stored)
     : in_(in), offset_(offset), area_(area), max_unit_(max_unit),
-      per_record_(per_record), left_(total),
+      min_stored_(min_stored), per_record_(per_record), left_(total),
       buf_(buffer_units(per_record, total) * (4 + max_unit)) {}
 
 int VarRecordReader::next(const uint8_t** unit, uint32_t* size,
@@ -184,7 +185,7 @@ int VarRecordReader::next(const uint8_t** unit, uint32_t* size,
   }
   *size = get_u32(&buf_[pos_ * 4]);
   *unit = &buf_[at_];
-  at_ += *size;
+  at_ += std::max<uint64_t>(*size, min_stored_);
   ++pos_;
   return kIoOk;
 }
@@ -204,9 +205,9 @@ int VarRecordReader::next_record(std::string* error) {
   if (get_u32(head) != want || get_u32(head + 12) != 0) {
     return fail(error, kIoInvalid, name + " has a wrong count");
   }
-  // Between one byte and max_unit per unit, inside the area, and the
-  // last record ends the area.
-  if (payload < want * 5 || payload > want * (4 + max_unit_) ||
+  // Between min_stored and max_unit bytes per unit, inside the area, and
+  // the last record ends the area.
+  if (payload < want * (4 + min_stored_) || payload > want * (4 + max_unit_) ||
       payload > area_ - kVarRecordHead ||
       (left_ == want && payload != area_ - kVarRecordHead)) {
     return fail(error, kIoInvalid, name + " has a wrong payload length");
@@ -225,7 +226,7 @@ int VarRecordReader::next_record(std::string* error) {
                   name + ": stored size " + std::to_string(size) +
                       " of its unit " + std::to_string(i) + " is out of range");
     }
-    sum += size;
+    sum += std::max(size, min_stored_);
   }
   if (sum != payload) {
     return fail(error, kIoInvalid, name + ": sizes disagree with the payload");
@@ -350,8 +351,10 @@ int RecordWriter::add(const uint8_t* data, uint64_t count) {
 }
 
 VarRecordWriter::VarRecordWriter(OutFile* out, uint64_t max_unit,
-                                 uint64_t per_record, uint64_t total)
-    : out_(out), max_unit_(max_unit), per_record_(per_record), left_(total) {}
+                                 uint64_t per_record, uint64_t total,
+                                 uint64_t min_stored)
+    : out_(out), max_unit_(max_unit), min_stored_(min_stored),
+      per_record_(per_record), left_(total) {}
 
 int VarRecordWriter::add(const uint8_t* unit, uint32_t size) {
   const uint64_t want = std::min(per_record_, left_);
@@ -359,8 +362,9 @@ int VarRecordWriter::add(const uint8_t* unit, uint32_t size) {
   uint8_t raw[4];
   put_u32(raw, size);
   sizes_.insert(sizes_.end(), raw, raw + 4);
-  units_.insert(units_.end(), unit, unit + size);
-  unit_bytes_ += size;
+  const uint64_t stored = std::max<uint64_t>(size, min_stored_);
+  units_.insert(units_.end(), unit, unit + stored);
+  unit_bytes_ += stored;
   if (++have_ < want) return kIoOk;
   uint8_t head[kVarRecordHead];
   put_u32(head, static_cast<uint32_t>(have_));

@@ -89,7 +89,9 @@ uint64_t record_stream_bytes(uint64_t total, uint64_t unit,
 // per_record) units, u32 count, u32 crc32c(payload), u32 payload_bytes,
 // u32 0, then the payload: count u32 sizes, then the units back to back.
 // Its length follows from the content, so the format keeps it in its
-// header.
+// header. A stream with `min_stored` above 1 (encrypted units, which take
+// at least a cipher block) stores max(size, min_stored) bytes per unit:
+// the sizes stay the true ones and the bytes past them are the writer's.
 constexpr uint64_t kVarRecordHead = 16;
 
 class InFile {
@@ -147,8 +149,10 @@ class RecordReader {
 class VarRecordReader {
  public:
   VarRecordReader(const InFile* in, uint64_t offset, uint64_t area,
-                  uint64_t max_unit, uint64_t per_record, uint64_t total);
-  // *unit points into the reader's buffer until the next call.
+                  uint64_t max_unit, uint64_t per_record, uint64_t total,
+                  uint64_t min_stored = 1);
+  // *unit points into the reader's buffer until the next call; it holds
+  // max(*size, min_stored) bytes.
   int next(const uint8_t** unit, uint32_t* size, std::string* error);
   // Units not yet handed out.
   uint64_t left() const { return left_ + (have_ - pos_); }
@@ -157,7 +161,7 @@ class VarRecordReader {
   int next_record(std::string* error);
 
   const InFile* in_;
-  uint64_t offset_, area_, max_unit_, per_record_;
+  uint64_t offset_, area_, max_unit_, min_stored_, per_record_;
   uint64_t left_;  // units in records not yet read
   uint64_t have_ = 0, pos_ = 0;  // units in buf_, units of them handed out
   uint64_t at_ = 0;  // of unit pos_ in buf_
@@ -214,19 +218,19 @@ class RecordWriter {
 class VarRecordWriter {
  public:
   VarRecordWriter(OutFile* out, uint64_t max_unit, uint64_t per_record,
-                  uint64_t total);
+                  uint64_t total, uint64_t min_stored = 1);
   // kIoFailed on a failed write, a size outside 1 .. max_unit or more
-  // units than announced.
+  // units than announced. `unit` holds max(size, min_stored) bytes.
   int add(const uint8_t* unit, uint32_t size);
   bool complete() const { return left_ == 0 && have_ == 0; }
   // Bytes of the records written so far: the stream's area once complete.
   uint64_t area() const { return area_; }
-  // Bytes of the units alone.
+  // Bytes of the units alone, as stored.
   uint64_t unit_bytes() const { return unit_bytes_; }
 
  private:
   OutFile* out_;
-  uint64_t max_unit_, per_record_;
+  uint64_t max_unit_, min_stored_, per_record_;
   uint64_t left_;  // units not yet written
   uint64_t have_ = 0;  // units in the open record
   uint64_t area_ = 0, unit_bytes_ = 0;

@@ -33,16 +33,28 @@
 // as many waves, 1 .. 4, as fit 64 KiB: compress 4 up to G = 2720, 3 up
 // to 4544, 2 up to 8192, 1 above; decompress 4 up to 5456, 3 up to 7280,
 // 2 up to 10912, 1 above.
+//
+// Keyed calls (compress.h): k_xts_var (crypt_ops.hip) replaces
+// k_gather_var, scratch slot -> registers -> ciphertext in pinned dense,
+// and on the way back turns pinned ciphertext into plaintext pieces in
+// device scratch, which the decode kernels then read in place of the
+// dense buffer, in strict mode (lz_decode): the host never sees a
+// plaintext piece, so the kernel's checks are the validation.
 
 #include <hip/hip_runtime.h>
 
+#include <string.h>
+
 #include <algorithm>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "crypt_internal.h"
 #include "gpu_internal.h"
 #include "hipstore/compress.h"
+#include "hipstore/crypt.h"
 #include "hipstore/engine.h"
 #include "marked_internal.h"
 
@@ -340,6 +352,12 @@ __device__ __forceinline__ bool lz_take_ext(const uint8_t* piece,
 // of them ends the decode with false. A match reads image[op - offset +
 // (i mod offset)], which lies below op for every i: correct down to
 // offset 1 without any order among the lanes.
+//
+// kStrict adds the end-of-block rules of lz_validate_granule (at least 5
+// final literals; no match starts after G - 12 or runs past G - 5), so
+// that the decode accepts exactly the pieces the host validators accept:
+// for the keyed calls, whose pieces the host sees only as ciphertext.
+template <bool kStrict = false>
 __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
                                           uint8_t* image, uint32_t start,
                                           uint32_t end, uint32_t lane) {
@@ -354,7 +372,7 @@ __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
     for (uint32_t i = lane; i < lit; i += 64) image[op + i] = piece[ip + i];
     ip += lit;
     op += lit;
-    if (ip == size) return op == end;
+    if (ip == size) return op == end && (!kStrict || lit >= 5);
     if (size - ip < 2) return false;
     const uint32_t offset = lz_byte(piece, ip) | lz_byte(piece, ip + 1) << 8;
     ip += 2;
@@ -363,6 +381,7 @@ __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
     if (len == 15 && !lz_take_ext(piece, size, ip, len)) return false;
     len += 4;
     if (len > end - op) return false;
+    if (kStrict && (end - op < 12 || len > end - 5 - op)) return false;
     wave_sync();  // the literals above may be the match's source
     const uint32_t from = op - offset;
     const uint32_t step = 64 % offset;
@@ -381,7 +400,9 @@ __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
 // offsets[slot]) becomes the marked granule of that rank; unmarked
 // granules are never written. bad[slot] is written for every piece of
 // the window: 0, or 1 when the piece could not be decoded, in which case
-// its granule is left alone.
+// its granule is left alone. kStrict: lz_decode's; `dense` is then the
+// device buffer k_xts_var decrypted the window into.
+template <bool kStrict = false>
 __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
     uint8_t* __restrict__ dst, const uint8_t* __restrict__ dense,
     const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
@@ -406,8 +427,9 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
     } else if (ok) {
       for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) piece16[i] = pp[i];
       wave_sync();
-      ok = lz_decode(reinterpret_cast<const uint8_t*>(piece16), size,
-                     reinterpret_cast<uint8_t*>(image16), 0, granule, lane);
+      ok = lz_decode<kStrict>(reinterpret_cast<const uint8_t*>(piece16), size,
+                              reinterpret_cast<uint8_t*>(image16), 0, granule,
+                              lane);
       wave_sync();
       if (ok) {
 #pragma unroll 4
@@ -425,6 +447,7 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
 // image[G, 2G) and only then writes the granule, so it reads its target
 // before it overwrites it; it touches no other granule, so waves need no
 // order. A raw piece is copied straight and reads nothing of `dst`.
+template <bool kStrict = false>
 __global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_decompress_marked(
     uint8_t* dst, const uint8_t* __restrict__ dense,
     const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
@@ -451,9 +474,9 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_decompress_marked(
 #pragma unroll 4
       for (uint32_t i = lane; i < n16; i += 64) image16[i] = pd[i];
       wave_sync();
-      ok = lz_decode(reinterpret_cast<const uint8_t*>(piece16), size,
-                     reinterpret_cast<uint8_t*>(image16), granule, 2 * granule,
-                     lane);
+      ok = lz_decode<kStrict>(reinterpret_cast<const uint8_t*>(piece16), size,
+                              reinterpret_cast<uint8_t*>(image16), granule,
+                              2 * granule, lane);
       wave_sync();
       if (ok) {
 #pragma unroll 4
@@ -522,15 +545,6 @@ CompressCtx& compress_ctx() {
   return ctx;
 }
 
-// Exclusive offsets of a window's padded pieces.
-void piece_offsets(const uint32_t* sizes, uint64_t count, uint64_t* offsets) {
-  uint64_t at = 0;
-  for (uint64_t i = 0; i < count; ++i) {
-    offsets[i] = at;
-    at += lz_padded(sizes[i]);
-  }
-}
-
 // Granule index of marked granule number `rank` (error messages).
 uint64_t granule_of_rank(const std::vector<uint64_t>& bitmap, uint64_t rank) {
   for (uint64_t w = 0; w < bitmap.size(); ++w) {
@@ -546,29 +560,78 @@ uint64_t granule_of_rank(const std::vector<uint64_t>& bitmap, uint64_t rank) {
   return bitmap.size() * 64;
 }
 
+// What a piece of `size` bytes takes of a window's dense stream. A keyed
+// call stores at least one cipher block per piece (min_piece = 16).
+uint64_t piece_room(uint32_t size, uint32_t min_piece) {
+  return lz_padded(std::max(size, min_piece));
+}
+
+// Exclusive offsets of a window's padded pieces.
+void piece_offsets(const uint32_t* sizes, uint64_t count, uint32_t min_piece,
+                   uint64_t* offsets) {
+  uint64_t at = 0;
+  for (uint64_t i = 0; i < count; ++i) {
+    offsets[i] = at;
+    at += piece_room(sizes[i], min_piece);
+  }
+}
+
+// The key of a keyed call: both directions' schedules for the host codec.
+// Null when the call has no key.
+struct LzKey {
+  const XtsSchedules* schedules = nullptr;
+  uint64_t first_unit = 0;
+  explicit operator bool() const { return schedules != nullptr; }
+  uint32_t min_piece() const { return schedules != nullptr ? 16 : 1; }
+};
+
+bool size_ok(uint32_t size, uint32_t granule) {
+  return size != 0 && size <= granule;
+}
+
+void name_bad_piece(const std::vector<uint64_t>& bitmap, uint64_t rank,
+                    const std::string& why, std::string* error) {
+  if (error != nullptr) {
+    *error = "granule " + std::to_string(granule_of_rank(bitmap, rank)) +
+             ": bad compressed piece (" + why + ")";
+  }
+}
+
 // Sizes, then every piece, of one window as a source delivered it;
 // fills `offsets`. kIoInvalid names the granule.
 int check_window(const std::vector<uint64_t>& bitmap, const uint8_t* data,
                  const uint32_t* sizes, uint64_t first_rank, uint64_t count,
-                 uint32_t granule, bool dictionary, uint64_t* offsets,
-                 std::string* error) {
+                 uint32_t granule, bool dictionary, uint32_t min_piece,
+                 uint64_t* offsets, std::string* error) {
   uint64_t at = 0;
   for (uint64_t i = 0; i < count; ++i) {
     std::string why = "stored size out of range";
-    if (sizes[i] == 0 || sizes[i] > granule ||
+    if (!size_ok(sizes[i], granule) ||
         !(dictionary
               ? lz_dict_validate_granule(data + at, sizes[i], granule, &why)
               : lz_validate_granule(data + at, sizes[i], granule, &why))) {
-      if (error != nullptr) {
-        *error = "granule " +
-                 std::to_string(granule_of_rank(bitmap, first_rank + i)) +
-                 ": bad compressed piece (" + why + ")";
-      }
+      name_bad_piece(bitmap, first_rank + i, why, error);
       return kIoInvalid;
     }
     offsets[i] = at;
-    at += lz_padded(sizes[i]);
+    at += piece_room(sizes[i], min_piece);
   }
+  return kIoOk;
+}
+
+// What the host can check of a keyed window, whose pieces are ciphertext:
+// the sizes. Fills `offsets`.
+int check_window_sizes(const std::vector<uint64_t>& bitmap,
+                       const uint32_t* sizes, uint64_t first_rank,
+                       uint64_t count, uint32_t granule, uint64_t* offsets,
+                       std::string* error) {
+  for (uint64_t i = 0; i < count; ++i) {
+    if (!size_ok(sizes[i], granule)) {
+      name_bad_piece(bitmap, first_rank + i, "stored size out of range", error);
+      return kIoInvalid;
+    }
+  }
+  piece_offsets(sizes, count, 16, offsets);
   return kIoOk;
 }
 
@@ -590,10 +653,17 @@ struct LzStream : HalvesStream {
   uint8_t* base;  // the bdev's range in device memory
   bool dictionary;
   const uint8_t* dict;  // the base volume's range in device memory
+  // A keyed call: k_xts_var encrypts the pieces on their way from scratch
+  // to `dense` and decrypts them on their way back into scratch, where
+  // the strict decode kernels read them. The copy of the schedules here
+  // is cleared with the object.
+  bool keyed;
+  uint64_t first_unit;
+  XtsKernelKeys keys;
 
   LzStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
-           const MarkedPlan& plan, bool compress, bool with_dictionary = false,
-           const uint8_t* dict_range = nullptr)
+           const MarkedPlan& plan, bool compress, const LzKey& key,
+           bool with_dictionary = false, const uint8_t* dict_range = nullptr)
       : HalvesStream(device), granule(granule_bytes),
         chunk(plan.chunk_granules),
         dense(compress_ctx().dense.reserve(2 * chunk * granule)),
@@ -602,9 +672,13 @@ struct LzStream : HalvesStream {
         bad(compress_ctx().bad.reserve(2 * chunk)),
         dev_words(device_view(plan.words)), dev_ranks(device_view(plan.ranks)),
         base(static_cast<uint8_t*>(bdev->device_base()) + offset),
-        dictionary(with_dictionary), dict(dict_range) {
-    if (compress) {
+        dictionary(with_dictionary), dict(dict_range),
+        keyed(static_cast<bool>(key)), first_unit(key.first_unit) {
+    if (keyed) xts_load_kernel_keys(*key.schedules, compress, &keys);
+    if (compress || keyed) {
       scratch = compress_ctx().scratch.reserve(device, 2 * chunk * granule);
+    }
+    if (compress) {
       for (hipEvent_t& e : packed) {
         HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       }
@@ -615,6 +689,7 @@ struct LzStream : HalvesStream {
     for (hipEvent_t e : packed) {
       if (e != nullptr) (void)hipEventDestroy(e);
     }
+    explicit_bzero(&keys, sizeof(keys));
   }
 
   void compress(const MarkedWindow& win, int half) {
@@ -643,7 +718,17 @@ struct LzStream : HalvesStream {
 
   // After packed[half]: the sizes are in, the pieces follow.
   void gather(const MarkedWindow& win, int half) {
-    piece_offsets(sizes + half * chunk, win.count, offsets + half * chunk);
+    piece_offsets(sizes + half * chunk, win.count, keyed ? 16 : 1,
+                  offsets + half * chunk);
+    if (keyed) {
+      xts_var_launch(true, stream, scratch + half * chunk * granule,
+                     device_view(dense + half * chunk * granule),
+                     device_view(sizes + half * chunk),
+                     device_view(offsets + half * chunk), dev_words, dev_ranks,
+                     win, granule, first_unit, keys);
+      HIP_CHECK(hipEventRecord(done[half], stream));
+      return;
+    }
     const uint32_t grid = std::min<uint32_t>(
         (win.count + kWavesPerWg - 1) / kWavesPerWg, 2048);
     hipLaunchKernelGGL(k_gather_var, dim3(grid), dim3(kWavesPerWg * 64), 0,
@@ -655,15 +740,28 @@ struct LzStream : HalvesStream {
     HIP_CHECK(hipEventRecord(done[half], stream));
   }
 
+  // Keyed: the window's sizes were checked (check_window_sizes), so the
+  // pieces at their offsets stay inside a half of scratch.
   void decompress(const MarkedWindow& win, int half) {
     const uint32_t per_wave = (dictionary ? 3 : 2) * granule;
     const uint32_t waves = dictionary ? lzd_waves(per_wave) : lz_waves(per_wave);
-    hipLaunchKernelGGL(dictionary ? k_lzd_decompress_marked
-                                  : k_lz_decompress_marked,
+    const uint8_t* pieces = device_view(dense + half * chunk * granule);
+    if (keyed) {
+      uint8_t* plain = scratch + half * chunk * granule;
+      xts_var_launch(false, stream, pieces, plain,
+                     device_view(sizes + half * chunk),
+                     device_view(offsets + half * chunk), dev_words, dev_ranks,
+                     win, granule, first_unit, keys);
+      pieces = plain;
+    }
+    hipLaunchKernelGGL(dictionary
+                           ? (keyed ? k_lzd_decompress_marked<true>
+                                    : k_lzd_decompress_marked<false>)
+                           : (keyed ? k_lz_decompress_marked<true>
+                                    : k_lz_decompress_marked<false>),
                        dim3(wave_window_grid(win, waves)),
                        dim3(waves * 64), waves * per_wave, stream, base,
-                       device_view(dense + half * chunk * granule),
-                       device_view(sizes + half * chunk),
+                       pieces, device_view(sizes + half * chunk),
                        device_view(offsets + half * chunk),
                        device_view(bad + half * chunk), dev_words, dev_ranks,
                        win, granule);
@@ -703,12 +801,22 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
                    const DecompressSource& source, uint64_t* unpacked,
                    std::string* error) {
   uint32_t in_half[2] = {0, 0};  // pieces of the kernel that last used it
-  // After that kernel: did it give up on a piece?
+  uint64_t rank_of[2] = {0, 0};  // rank of the first of them
+  // After that kernel: did it give up on a piece? On a keyed call the
+  // strict decode is the validation, so that piece is a bad file and is
+  // named as host validation names it; otherwise the host had accepted it.
   auto gave_up = [&](int half) {
     const uint8_t* bad = ls.bad + half * ls.chunk;
-    return std::any_of(bad, bad + in_half[half],
-                       [](uint8_t b) { return b != 0; });
+    const uint8_t* first = std::find_if(bad, bad + in_half[half],
+                                        [](uint8_t b) { return b != 0; });
+    if (first == bad + in_half[half]) return false;
+    if (ls.keyed && (error == nullptr || error->empty())) {
+      name_bad_piece(bitmap, rank_of[half] + static_cast<uint64_t>(first - bad),
+                     "refused by the strict decoder", error);
+    }
+    return true;
   };
+  const int gave_up_status = ls.keyed ? kIoInvalid : kIoFailed;
   uint64_t g_begin = 0;
   uint64_t launched = 0;
   int status = kIoOk;
@@ -717,7 +825,7 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
     // The kernel two windows back read this half: let it finish first.
     if (in_half[half] != 0) {
       wait_marked_event(ls.done[half]);
-      if (gave_up(half)) status = kIoFailed;
+      if (gave_up(half)) status = gave_up_status;
       in_half[half] = 0;
       if (status != kIoOk) break;
     }
@@ -725,19 +833,26 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
     uint32_t* sizes = ls.sizes + half * ls.chunk;
     status = source(data, sizes, win.first_rank, win.count);
     if (status == 0) {
-      status = check_window(bitmap, data, sizes, win.first_rank, win.count,
-                            ls.granule, ls.dictionary,
-                            ls.offsets + half * ls.chunk, error);
+      status = ls.keyed
+                   ? check_window_sizes(bitmap, sizes, win.first_rank,
+                                        win.count, ls.granule,
+                                        ls.offsets + half * ls.chunk, error)
+                   : check_window(bitmap, data, sizes, win.first_rank,
+                                  win.count, ls.granule, ls.dictionary, 1,
+                                  ls.offsets + half * ls.chunk, error);
     }
     if (status != kIoOk) break;
     ls.decompress(win, half);
     in_half[half] = win.count;
+    rank_of[half] = win.first_rank;
     launched += win.count;
     g_begin = win.g_end;
   }
   HIP_CHECK(hipStreamSynchronize(ls.stream));
-  if (gave_up(0) || gave_up(1)) {
-    if (status == kIoOk) status = kIoFailed;
+  // The older window first, so that the lowest bad granule is named.
+  const int older = rank_of[0] <= rank_of[1] ? 0 : 1;
+  if (gave_up(older) || gave_up(older ^ 1)) {
+    if (status == kIoOk) status = gave_up_status;
     if (error != nullptr && error->empty()) {
       *error = ls.dictionary ? "k_lzd_decompress_marked gave up on a piece"
                              : "k_lz_decompress_marked gave up on a piece";
@@ -777,12 +892,13 @@ struct MarkCursor {
 // Generic paths: bdev_pack_marked_sync / bdev_unpack_marked_sync cut the
 // chunks, the host codec does the rest. With `base` (HSLZD1) the
 // dictionary of every granule is read from it, one granule (at most 16
-// KiB) per read.
+// KiB) per read. With `key` every piece is one HSXTS2 unit
+// (xts_encrypt_var / xts_decrypt_var) in the keyed layout.
 int compress_generic(Bdev* src, uint64_t offset, Bdev* base,
                      uint64_t base_offset, uint64_t length, uint32_t granule,
                      const std::vector<uint64_t>& bitmap,
                      uint64_t staging_bytes, const CompressSink& sink,
-                     uint64_t* packed) {
+                     const LzKey& key, uint64_t* packed) {
   std::vector<uint8_t> pieces;
   std::vector<uint32_t> sizes;
   std::vector<uint8_t> dict(base != nullptr ? granule : 0);
@@ -794,18 +910,22 @@ int compress_generic(Bdev* src, uint64_t offset, Bdev* base,
         sizes.resize(count);
         uint64_t at = 0;
         for (uint64_t i = 0; i < count; ++i) {
+          const uint64_t g = marks.next();
+          uint8_t* piece = pieces.data() + at;
           if (base != nullptr) {
-            const int status = bdev_read_sync(
-                base, base_offset + marks.next() * granule, dict.data(),
-                granule);
+            const int status = bdev_read_sync(base, base_offset + g * granule,
+                                              dict.data(), granule);
             if (status != kIoOk) return status;
             sizes[i] = lz_dict_compress_granule(data + i * granule, dict.data(),
-                                                granule, pieces.data() + at);
+                                                granule, piece);
           } else {
-            sizes[i] = lz_compress_granule(data + i * granule, granule,
-                                           pieces.data() + at);
+            sizes[i] = lz_compress_granule(data + i * granule, granule, piece);
           }
-          at += lz_padded(sizes[i]);
+          if (key) {
+            xts_encrypt_var(*key.schedules, key.first_unit + g, piece, piece,
+                            std::max(sizes[i], 16u));
+          }
+          at += piece_room(sizes[i], key.min_piece());
         }
         return sink(pieces.data(), sizes.data(), first_rank, count);
       },
@@ -816,10 +936,12 @@ int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
                        uint32_t granule, const std::vector<uint64_t>& bitmap,
                        uint64_t staging_bytes,
                        const DecompressSource& source, bool dictionary,
-                       uint64_t* unpacked, std::string* error) {
+                       const LzKey& key, uint64_t* unpacked,
+                       std::string* error) {
   std::vector<uint8_t> pieces;
   std::vector<uint32_t> sizes;
   std::vector<uint64_t> offsets;
+  std::vector<uint64_t> index;  // of each granule of the chunk
   std::vector<uint8_t> dict(dictionary ? granule : 0);
   MarkCursor marks{bitmap, length / granule};
   // A chunk is written after this returns, and no earlier chunk holds
@@ -830,11 +952,24 @@ int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
         pieces.resize(count * granule);
         sizes.resize(count);
         offsets.resize(count);
+        index.resize(count);
+        for (uint64_t& g : index) g = marks.next();
         int status = source(pieces.data(), sizes.data(), first_rank, count);
+        if (status == 0 && key) {
+          // Decrypted in place up to the first size that is out of range,
+          // which check_window refuses before it looks at a piece.
+          uint64_t at = 0;
+          for (uint64_t i = 0; i < count && size_ok(sizes[i], granule); ++i) {
+            xts_decrypt_var(*key.schedules, key.first_unit + index[i],
+                            pieces.data() + at, pieces.data() + at,
+                            std::max(sizes[i], 16u));
+            at += piece_room(sizes[i], 16);
+          }
+        }
         if (status == 0) {
           status = check_window(bitmap, pieces.data(), sizes.data(), first_rank,
-                                count, granule, dictionary, offsets.data(),
-                                error);
+                                count, granule, dictionary, key.min_piece(),
+                                offsets.data(), error);
         }
         for (uint64_t i = 0; status == kIoOk && i < count; ++i) {
           if (!dictionary) {
@@ -842,7 +977,7 @@ int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
                                   data + i * granule);
             continue;
           }
-          status = bdev_read_sync(dst, offset + marks.next() * granule,
+          status = bdev_read_sync(dst, offset + index[i] * granule,
                                   dict.data(), granule);
           if (status == kIoOk) {
             lz_dict_decompress_granule(pieces.data() + offsets[i], sizes[i],
@@ -856,19 +991,29 @@ int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
 }
 
 // Validation and plan of both calls; chunking as marked_stream_sync.
-// kIoOk with plan->marked == 0 means nothing to do.
+// kIoOk with plan->marked == 0 means nothing to do. A key (any of the
+// two arguments set) must pass xts_key_ok and leave every unit number
+// below 2^64-1.
 int lz_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
             const std::vector<uint64_t>& bitmap, uint64_t staging_bytes,
-            bool have_callback, MarkedPlan* plan, std::string* error) {
+            bool have_callback, const uint8_t* key, size_t key_len,
+            uint64_t first_unit, MarkedPlan* plan, std::string* error) {
   if (!lz_granule_ok(granule)) {
     if (error != nullptr) {
       *error = "compression needs 512 <= granule <= 16384, a multiple of 16";
     }
     return kIoInvalid;
   }
+  if ((key != nullptr || key_len != 0) && !xts_key_ok(key, key_len)) {
+    if (error != nullptr) {
+      *error = "the key must be 64 bytes whose halves differ";
+    }
+    return kIoInvalid;
+  }
   if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule,
                          &bitmap) ||
-      (staging_bytes != 0 && staging_bytes < granule)) {
+      (staging_bytes != 0 && staging_bytes < granule) ||
+      (key != nullptr && length / granule > kXtsKcvUnit - first_unit)) {
     return kIoInvalid;
   }
   *plan = build_marked_plan(length / granule, bitmap, true);
@@ -880,28 +1025,43 @@ int lz_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
   return kIoOk;
 }
 
+// The schedules of a call's key, if it has one, for as long as the call
+// runs.
+struct CallKey {
+  std::unique_ptr<XtsSchedules> schedules;
+  LzKey key;
+  CallKey(const uint8_t* raw, uint64_t first_unit) {
+    if (raw == nullptr) return;
+    schedules.reset(new XtsSchedules(raw));
+    key = {schedules.get(), first_unit};
+  }
+};
+
 }  // namespace
 
 int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               uint32_t granule,
                               const std::vector<uint64_t>& bitmap,
                               uint64_t staging_bytes, const CompressSink& sink,
-                              uint64_t* packed_out, std::string* error) {
+                              uint64_t* packed_out, std::string* error,
+                              const uint8_t* key, size_t key_len,
+                              uint64_t first_unit) {
   uint64_t unused = 0;
   uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
   *packed = 0;
   try {
     MarkedPlan plan;
     const int status = lz_plan(src, src_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(sink), &plan,
-                               error);
+                               staging_bytes, static_cast<bool>(sink), key,
+                               key_len, first_unit, &plan, error);
     if (status != kIoOk || plan.marked == 0) return status;
+    const CallKey call(key, first_unit);
     const int device = granule_kernel_device(src, src);
     if (device < 0) {
       return compress_generic(src, src_offset, nullptr, 0, length, granule,
-                              bitmap, staging_bytes, sink, packed);
+                              bitmap, staging_bytes, sink, call.key, packed);
     }
-    LzStream ls(device, src, src_offset, granule, plan, true);
+    LzStream ls(device, src, src_offset, granule, plan, true, call.key);
     return compress_gpu(ls, plan, sink, packed);
   } catch (const std::exception&) {
     return kIoFailed;
@@ -913,22 +1073,26 @@ int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 const std::vector<uint64_t>& bitmap,
                                 uint64_t staging_bytes,
                                 const DecompressSource& source,
-                                uint64_t* unpacked_out, std::string* error) {
+                                uint64_t* unpacked_out, std::string* error,
+                                const uint8_t* key, size_t key_len,
+                                uint64_t first_unit) {
   uint64_t unused = 0;
   uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
   *unpacked = 0;
   try {
     MarkedPlan plan;
     const int status = lz_plan(dst, dst_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(source), &plan,
-                               error);
+                               staging_bytes, static_cast<bool>(source), key,
+                               key_len, first_unit, &plan, error);
     if (status != kIoOk || plan.marked == 0) return status;
+    const CallKey call(key, first_unit);
     const int device = granule_kernel_device(dst, dst);
     if (device < 0) {
       return decompress_generic(dst, dst_offset, length, granule, bitmap,
-                                staging_bytes, source, false, unpacked, error);
+                                staging_bytes, source, false, call.key,
+                                unpacked, error);
     }
-    LzStream ls(device, dst, dst_offset, granule, plan, false);
+    LzStream ls(device, dst, dst_offset, granule, plan, false, call.key);
     return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
   } catch (const std::exception&) {
     return kIoFailed;
@@ -941,7 +1105,9 @@ int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
                                    const std::vector<uint64_t>& bitmap,
                                    uint64_t staging_bytes,
                                    const CompressSink& sink,
-                                   uint64_t* packed_out, std::string* error) {
+                                   uint64_t* packed_out, std::string* error,
+                                   const uint8_t* key, size_t key_len,
+                                   uint64_t first_unit) {
   uint64_t unused = 0;
   uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
   *packed = 0;
@@ -963,15 +1129,17 @@ int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
     }
     MarkedPlan plan;
     const int status = lz_plan(src, src_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(sink), &plan,
-                               error);
+                               staging_bytes, static_cast<bool>(sink), key,
+                               key_len, first_unit, &plan, error);
     if (status != kIoOk || plan.marked == 0) return status;
+    const CallKey call(key, first_unit);
     const int device = granule_kernel_device(src, base);
     if (device < 0) {
       return compress_generic(src, src_offset, base, base_offset, length,
-                              granule, bitmap, staging_bytes, sink, packed);
+                              granule, bitmap, staging_bytes, sink, call.key,
+                              packed);
     }
-    LzStream ls(device, src, src_offset, granule, plan, true, true,
+    LzStream ls(device, src, src_offset, granule, plan, true, call.key, true,
                 static_cast<const uint8_t*>(base->device_base()) + base_offset);
     return compress_gpu(ls, plan, sink, packed);
   } catch (const std::exception&) {
@@ -985,22 +1153,25 @@ int bdev_dict_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                      uint64_t staging_bytes,
                                      const DecompressSource& source,
                                      uint64_t* unpacked_out,
-                                     std::string* error) {
+                                     std::string* error, const uint8_t* key,
+                                     size_t key_len, uint64_t first_unit) {
   uint64_t unused = 0;
   uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
   *unpacked = 0;
   try {
     MarkedPlan plan;
     const int status = lz_plan(dst, dst_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(source), &plan,
-                               error);
+                               staging_bytes, static_cast<bool>(source), key,
+                               key_len, first_unit, &plan, error);
     if (status != kIoOk || plan.marked == 0) return status;
+    const CallKey call(key, first_unit);
     const int device = granule_kernel_device(dst, dst);
     if (device < 0) {
       return decompress_generic(dst, dst_offset, length, granule, bitmap,
-                                staging_bytes, source, true, unpacked, error);
+                                staging_bytes, source, true, call.key, unpacked,
+                                error);
     }
-    LzStream ls(device, dst, dst_offset, granule, plan, false, true);
+    LzStream ls(device, dst, dst_offset, granule, plan, false, call.key, true);
     return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
   } catch (const std::exception&) {
     return kIoFailed;

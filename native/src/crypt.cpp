@@ -1,5 +1,5 @@
-// The HSXTS1 host codec (hipstore/crypt.h): AES-256 byte by byte and XTS
-// over one data unit. It is the byte model of the kernels in
+// The HSXTS1 and HSXTS2 host codec (hipstore/crypt.h): AES-256 byte by
+// byte and XTS over one data unit, with ciphertext stealing for HSXTS2. It is the byte model of the kernels in
 // crypt_ops.hip and shares nothing with them: the S-box is derived from
 // the field inverse here and written out there, rounds are S-box,
 // ShiftRows and xtime here and T-tables there, decryption is the
@@ -196,6 +196,60 @@ void xts_encrypt_unit(const XtsSchedules& keys, uint64_t unit,
 void xts_decrypt_unit(const XtsSchedules& keys, uint64_t unit,
                       const uint8_t* in, uint8_t* out, uint32_t bytes) {
   xts_unit(keys, unit, in, out, bytes, aes256_decrypt_block);
+}
+
+namespace {
+
+// HSXTS2 over n = 16 * m + b bytes, m >= 1. The whole blocks but the last
+// go through xts_unit; `t` is then doubled up to T_{m-1}, `t_next` is
+// T_m. Encryption uses T_{m-1} first and T_m second, decryption the
+// other way round.
+template <typename Block>
+void xts_var(const XtsSchedules& keys, uint64_t unit, const uint8_t* in,
+             uint8_t* out, uint32_t bytes, bool encrypt, Block block) {
+  const uint32_t b = bytes % 16;
+  if (b == 0) {
+    xts_unit(keys, unit, in, out, bytes, block);
+    return;
+  }
+  const uint32_t last = bytes - b - 16;  // where block m-1 starts
+  xts_unit(keys, unit, in, out, last, block);
+  uint8_t t[16];
+  uint8_t t_next[16];
+  uint8_t x[16];
+  uint8_t tail[16];
+  first_tweak(keys, unit, t);
+  for (uint32_t at = 0; at < last; at += 16) tweak_double(t);
+  memcpy(t_next, t, 16);
+  tweak_double(t_next);
+  const uint8_t* first = encrypt ? t : t_next;
+  const uint8_t* second = encrypt ? t_next : t;
+  memcpy(tail, in + last + 16, b);  // before out overwrites it (in == out)
+  for (int i = 0; i < 16; ++i) x[i] = in[last + i] ^ first[i];
+  block(keys.k1_enc, x, x);
+  for (int i = 0; i < 16; ++i) x[i] ^= first[i];
+  // x is CC (or PP): its head is the stored tail, its rest is stolen.
+  memcpy(out + last + 16, x, b);
+  memcpy(x, tail, b);
+  for (int i = 0; i < 16; ++i) x[i] ^= second[i];
+  block(keys.k1_enc, x, x);
+  for (int i = 0; i < 16; ++i) out[last + i] = x[i] ^ second[i];
+  explicit_bzero(t, sizeof(t));
+  explicit_bzero(t_next, sizeof(t_next));
+  explicit_bzero(x, sizeof(x));
+  explicit_bzero(tail, sizeof(tail));
+}
+
+}  // namespace
+
+void xts_encrypt_var(const XtsSchedules& keys, uint64_t unit,
+                     const uint8_t* in, uint8_t* out, uint32_t bytes) {
+  xts_var(keys, unit, in, out, bytes, true, aes256_encrypt_block);
+}
+
+void xts_decrypt_var(const XtsSchedules& keys, uint64_t unit,
+                     const uint8_t* in, uint8_t* out, uint32_t bytes) {
+  xts_var(keys, unit, in, out, bytes, false, aes256_decrypt_block);
 }
 
 uint32_t xts_kcv(const uint8_t key[kXtsKeyBytes]) {

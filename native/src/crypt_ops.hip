@@ -2,7 +2,9 @@
 // host codec in hipstore/crypt.h, crypt.cpp): k_xts_pack_marked gathers
 // and encrypts in one pass, k_xts_unpack_marked decrypts and scatters;
 // their window loops and the generic path. Like bulk_ops.hip, each call
-// owns its stream, runs to completion and returns.
+// owns its stream, runs to completion and returns. k_xts_var (HSXTS2,
+// ciphertext stealing) encrypts and decrypts the variable-length pieces
+// of compress_ops.hip, which launches it through crypt_internal.h.
 //
 // Work split: as compress_ops.hip. A wave takes one whole granule at a
 // time and waves grid-stride over the granules of the window's bitmap
@@ -56,6 +58,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "crypt_internal.h"
 #include "gpu_internal.h"
 #include "hipstore/crypt.h"
 #include "hipstore/engine.h"
@@ -71,12 +74,6 @@ namespace {
 
 constexpr uint32_t kTableCopies = 8;
 constexpr uint32_t kXtsThreads = 256;  // one table entry per thread
-
-// Little-endian words of two 240-byte schedules.
-struct XtsKernelKeys {
-  uint32_t data[60];   // K1: encryption, or equivalent inverse cipher
-  uint32_t tweak[60];  // K2: encryption
-};
 
 __constant__ uint8_t kAesSbox[256] = {
     0x63, 0x7c, 0x77, 0x7b, 0xf2, 0x6b, 0x6f, 0xc5, 0x30, 0x01, 0x67, 0x2b,
@@ -354,6 +351,139 @@ __global__ __launch_bounds__(kXtsThreads) void k_xts_unpack_marked(
                     win, granule, first_unit, keys, tables);
 }
 
+// --- HSXTS2: units of any length, for compressed pieces ---------------------
+
+// 0xFF in the first n bytes of a block (n <= 16), 0 in the rest.
+__device__ __forceinline__ uint4 head_mask(uint32_t n) {
+  const uint64_t lo = n >= 8 ? ~0ull : (1ull << (8 * n)) - 1;
+  const uint64_t hi = n >= 16 ? ~0ull : n <= 8 ? 0 : (1ull << (8 * (n - 8))) - 1;
+  return make_uint4(static_cast<uint32_t>(lo), static_cast<uint32_t>(lo >> 32),
+                    static_cast<uint32_t>(hi), static_cast<uint32_t>(hi >> 32));
+}
+
+// The first n bytes of `head`, then `rest` from byte n on.
+__device__ __forceinline__ uint4 splice(uint4 head, uint4 rest, uint32_t n) {
+  const uint4 m = head_mask(n);
+  return make_uint4((head.x & m.x) | (rest.x & ~m.x),
+                    (head.y & m.y) | (rest.y & ~m.y),
+                    (head.z & m.z) | (rest.z & ~m.z),
+                    (head.w & m.w) | (rest.w & ~m.w));
+}
+
+// One XTS block under tweak t.
+template <bool kEncrypt>
+__device__ __forceinline__ uint4 xts_block(const XtsTables& tables,
+                                           const XtsKernelKeys& keys, uint4 x,
+                                           Tweak t) {
+  const uint4 mask = make_uint4(static_cast<uint32_t>(t.lo),
+                                static_cast<uint32_t>(t.lo >> 32),
+                                static_cast<uint32_t>(t.hi),
+                                static_cast<uint32_t>(t.hi >> 32));
+  x.x ^= mask.x;
+  x.y ^= mask.y;
+  x.z ^= mask.z;
+  x.w ^= mask.w;
+  x = kEncrypt ? aes_encrypt(tables, keys.data, x)
+               : aes_decrypt(tables, keys.data, x);
+  x.x ^= mask.x;
+  x.y ^= mask.y;
+  x.z ^= mask.z;
+  x.w ^= mask.w;
+  return x;
+}
+
+// The pieces of a window, each one HSXTS2 unit (crypt.h): wave per piece
+// over the window's bitmap, because the unit number is the granule's
+// index, not its rank. Encrypt reads piece r from slot r of `from`
+// (stride G, device scratch of the compress kernels) and writes
+// ciphertext to to + offsets[r] (pinned): it takes k_gather_var's place
+// and plaintext pieces never leave device memory. Decrypt reads
+// ciphertext at from + offsets[r] (pinned) and writes plaintext to to +
+// offsets[r] (device scratch), where the LZ decode kernels find their
+// pieces as if they were the dense buffer.
+//
+// Lane l owns blocks l, l + 64, ... and their tweaks as in xts_window.
+// With n = 16 * m + b, b != 0, the pair (m-1, m) belongs to the lane that
+// owns block m-1: it loads the partial block m as well, T_m is one more
+// step * alpha from its own tweak, and it runs the second cipher call
+// after its first, so CC never leaves its registers. Nothing crosses
+// lanes or the row step, so m % 64 == 0 (block m in the next row, which
+// is then never entered) is no special case, and decryption is the same
+// code with the two tweaks swapped; giving block m to the next lane
+// instead would make decryption send C_{m-1} up a lane and CC back down,
+// across rows when m % 64 == 0. The price is that the pair's lane runs
+// two cipher calls in sequence while its row's other lanes wait: one
+// block time per piece.
+//
+// Every global access is 16 bytes per lane. Tails are cut and spliced in
+// registers; the stored tail block is written with its pad as zero, and a
+// piece of fewer than 16 bytes is one zero-padded block. The size is cut
+// to G, so with G % 16 == 0 block m of a piece with b != 0 ends inside
+// the slot; nothing depends on data or key except the table index.
+template <bool kEncrypt>
+__global__ __launch_bounds__(kXtsThreads) void k_xts_var(
+    const uint8_t* __restrict__ from, uint8_t* __restrict__ to,
+    const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
+    const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
+    uint32_t granule, uint64_t first_unit, XtsKernelKeys keys) {
+  __shared__ uint32_t te[256 * kTableCopies];
+  __shared__ uint32_t td[kEncrypt ? 1 : 256 * kTableCopies];
+  __shared__ uint8_t sbox[256];
+  __shared__ uint8_t isbox[kEncrypt ? 1 : 256];
+  __shared__ uint32_t tweak_rk[60];
+  xts_build_tables<kEncrypt>(te, td, sbox, isbox, tweak_rk, keys);
+  const XtsTables tables = {te, td, sbox, isbox, tweak_rk,
+                            threadIdx.x & (kTableCopies - 1)};
+  const uint32_t lane = threadIdx.x & 63;
+  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
+                                                      uint32_t slot) {
+    const uint32_t size = min(uniform(sizes[slot]), granule);
+    if (size == 0) return;  // no such piece: nothing to move
+    const uint32_t n = max(size, 16u);
+    const uint32_t m = n >> 4;  // whole blocks, >= 1
+    const uint32_t b = n & 15;  // bytes of block m
+    const uint64_t unit = first_unit + g;  // wave-uniform
+    asm volatile("" ::: "memory");  // K2's schedule stays in LDS
+    const uint4 t0 = aes_encrypt(
+        tables, tables.tweak_rk,
+        make_uint4(static_cast<uint32_t>(unit),
+                   static_cast<uint32_t>(unit >> 32), 0, 0));
+    Tweak t = {static_cast<uint64_t>(t0.y) << 32 | t0.x,
+               static_cast<uint64_t>(t0.w) << 32 | t0.z};
+    t = tweak_shift_if<1>(t, lane);
+    t = tweak_shift_if<2>(t, lane);
+    t = tweak_shift_if<4>(t, lane);
+    t = tweak_shift_if<8>(t, lane);
+    t = tweak_shift_if<16>(t, lane);
+    t = tweak_shift_if<32>(t, lane);
+    const uint64_t at = offsets[slot];
+    const uint4* __restrict__ pin = reinterpret_cast<const uint4*>(
+        kEncrypt ? from + static_cast<uint64_t>(slot) * granule : from + at);
+    uint4* __restrict__ pout = reinterpret_cast<uint4*>(to + at);
+    for (uint32_t row = 0; row < m; row += 64, t = tweak_next_row(t)) {
+      const uint32_t i = row + lane;
+      if (i >= m) continue;  // past the whole blocks in the last row
+      uint4 x = pin[i];
+      if (kEncrypt) x = splice(x, make_uint4(0, 0, 0, 0), min(size, 16u));
+      const bool steal = b != 0 && i == m - 1;
+      const Tweak t_next = tweak_shift<1>(t);
+      // Encryption runs block m-1 under T_{m-1}, then the spliced block
+      // under T_m; decryption the other way round.
+      x = xts_block<kEncrypt>(tables, keys, x,
+                              steal && !kEncrypt ? t_next : t);
+      if (steal) {
+        const uint4 tail = pin[m];
+        pout[m] = splice(x, make_uint4(0, 0, 0, 0), b);
+        x = xts_block<kEncrypt>(tables, keys, splice(tail, x, b),
+                                kEncrypt ? t_next : t);
+      }
+      if (!kEncrypt) x = splice(x, make_uint4(0, 0, 0, 0), min(size, 16u));
+      pout[i] = x;
+    }
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Window loops
 // ---------------------------------------------------------------------------
@@ -396,8 +526,7 @@ struct XtsStream : HalvesStream {
         dev_staging(device_view(staging)), dev_words(device_view(plan.words)),
         dev_ranks(device_view(plan.ranks)),
         base(static_cast<uint8_t*>(bdev->device_base()) + offset) {
-    load_words(encrypt ? schedules.k1_enc : schedules.k1_dec, keys.data);
-    load_words(schedules.k2_enc, keys.tweak);
+    xts_load_kernel_keys(schedules, encrypt, &keys);
   }
   ~XtsStream() { explicit_bzero(&keys, sizeof(keys)); }
 
@@ -543,6 +672,25 @@ int xts_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
 }
 
 }  // namespace
+
+void xts_load_kernel_keys(const XtsSchedules& schedules, bool encrypt,
+                          XtsKernelKeys* keys) {
+  load_words(encrypt ? schedules.k1_enc : schedules.k1_dec, keys->data);
+  load_words(schedules.k2_enc, keys->tweak);
+}
+
+void xts_var_launch(bool encrypt, hipStream_t stream, const uint8_t* from,
+                    uint8_t* to, const uint32_t* sizes, const uint64_t* offsets,
+                    const unsigned long long* bitmap,
+                    const uint32_t* rank_before_word, const MarkedWindow& win,
+                    uint32_t granule, uint64_t first_unit,
+                    const XtsKernelKeys& keys) {
+  hipLaunchKernelGGL(encrypt ? k_xts_var<true> : k_xts_var<false>,
+                     dim3(wave_window_grid(win, kXtsThreads / 64)),
+                     dim3(kXtsThreads), 0, stream, from, to, sizes, offsets,
+                     bitmap, rank_before_word, win, granule, first_unit, keys);
+  HIP_CHECK(hipGetLastError());
+}
 
 int bdev_xts_pack_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               uint32_t granule,

@@ -8,6 +8,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "checked_file.h"
@@ -38,6 +39,9 @@ const Format kDeltaXts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
 const Format kDeltaDict = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
                            {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
                            kDeltaVersionDict, "delta file"};
+const Format kDeltaCts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
+                          {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
+                          kDeltaVersionCts, "delta file"};
 const Format kMap = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
                      {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
                      kFingerprintMapVersion, "fingerprint map"};
@@ -90,9 +94,21 @@ struct ParsedDelta {
   DeltaInfo info;
   std::vector<uint64_t> bitmap;
   uint64_t records_offset = 0;
-  uint64_t record_area = 0;  // version 2
-  uint32_t kcv = 0;          // version 3
+  uint64_t record_area = 0;  // compressed files
+  uint32_t kcv = 0;          // encrypted files
 };
+
+// The key block of a version-5 file, directly after the bitmap: "HSKC",
+// u32 xts_kcv(key), u32 0, u32 crc32c of those 12 bytes.
+constexpr uint64_t kKeyBlockBytes = 16;
+const char kKeyBlockMagic[4] = {'H', 'S', 'K', 'C'};
+
+void put_key_block(uint8_t* block, uint32_t kcv) {
+  memcpy(block, kKeyBlockMagic, 4);
+  put_u32(block + 4, kcv);
+  put_u32(block + 8, 0);
+  put_u32(block + 12, crc32c_sw(0, block, 12));
+}
 
 // The structural pass: everything that can be checked without reading
 // a record payload.
@@ -100,14 +116,19 @@ int parse_delta(const std::string& path, ParsedDelta* out,
                 std::string* error) {
   InFile& in = out->in;
   int status =
-      in.open(path, kDelta, error, {&kDeltaLz, &kDeltaXts, &kDeltaDict});
+      in.open(path, kDelta, error,
+              {&kDeltaLz, &kDeltaXts, &kDeltaDict, &kDeltaCts});
   if (status != kIoOk) return status;
   const Header& h = in.header;
   DeltaInfo& info = out->info;
   info.version = in.format().version;
-  info.dictionary = info.version == kDeltaVersionDict;
-  info.compressed = info.version == kDeltaVersionLz || info.dictionary;
-  info.encrypted = info.version == kDeltaVersionXts;
+  // Version 5 is compressed and encrypted, with or without dictionaries:
+  // there the flag decides, everywhere else the version does.
+  const bool cts = info.version == kDeltaVersionCts;
+  info.dictionary = cts ? (h.word & kDeltaFlagDict) != 0
+                        : info.version == kDeltaVersionDict;
+  info.compressed = info.version == kDeltaVersionLz || info.dictionary || cts;
+  info.encrypted = info.version == kDeltaVersionXts || cts;
   info.block_size = h.block_size;
   info.granule = h.granule;
   info.full = (h.word & kDeltaFlagFull) != 0;
@@ -115,7 +136,8 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   info.n_granules = h.n_granules;
   info.n_marked = get_u64(h.owned);
   info.file_bytes = in.file_bytes;
-  // The spare words: version 1 none, version 2 both, version 3 the first.
+  // The spare words: version 1 none, versions 2, 4 and 5 both, version 3
+  // the first.
   if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz | kDeltaFlagXts |
                   kDeltaFlagDict)) != 0 ||
       ((h.word & kDeltaFlagLz) != 0) != info.compressed ||
@@ -129,7 +151,7 @@ int parse_delta(const std::string& path, ParsedDelta* out,
     if (!xts_granule_ok(info.granule)) {
       return fail(error, kIoInvalid, "granule outside the encrypted range");
     }
-    out->kcv = get_u32(h.owned + 12);
+    if (!cts) out->kcv = get_u32(h.owned + 12);
   }
   if (!geometry_ok(h.block_size, h.granule, h.volume_bytes, h.n_granules) ||
       info.n_marked > info.n_granules ||
@@ -149,14 +171,15 @@ int parse_delta(const std::string& path, ParsedDelta* out,
     const uint64_t fixed =
         (records - info.stored_bytes) * 2 + info.n_marked * 4;
     out->record_area = get_u64(h.owned + 12);
-    if (out->record_area < fixed + info.n_marked ||
+    if (out->record_area < fixed + info.n_marked * (cts ? 16 : 1) ||
         out->record_area > fixed + info.stored_bytes) {
       return fail(error, kIoInvalid, "record_area_bytes out of range");
     }
     info.stored_bytes = out->record_area - fixed;
     records = out->record_area;
   }
-  status = in.check_length(n_words * 8 + records, error);
+  const uint64_t key_block = cts ? kKeyBlockBytes : 0;
+  status = in.check_length(n_words * 8 + key_block + records, error);
   if (status != kIoOk) return status;
   std::vector<uint8_t> raw(n_words * 8);
   if (!in.read(raw.data(), raw.size(), kHeaderBytes)) {
@@ -176,7 +199,18 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   if (popcount(out->bitmap) != info.n_marked) {
     return fail(error, kIoInvalid, "n_marked disagrees with the bitmap");
   }
-  out->records_offset = kHeaderBytes + raw.size();
+  out->records_offset = kHeaderBytes + raw.size() + key_block;
+  if (cts) {
+    uint8_t block[kKeyBlockBytes];
+    if (!in.read(block, sizeof(block), kHeaderBytes + raw.size())) {
+      return fail(error, kIoFailed, "cannot read key block");
+    }
+    if (memcmp(block, kKeyBlockMagic, 4) != 0 || get_u32(block + 8) != 0 ||
+        crc32c_sw(0, block, 12) != get_u32(block + 12)) {
+      return fail(error, kIoInvalid, "bad key block");
+    }
+    out->kcv = get_u32(block + 4);
+  }
   return in.check_trailer(info.n_marked, error);
 }
 
@@ -184,42 +218,58 @@ int parse_delta(const std::string& path, ParsedDelta* out,
 // (bdev_compress_marked_sync) and record_area_bytes put into the header
 // once the records are out. With info->dictionary the version-4 file:
 // the same, compressed against `base` (bdev_dict_compress_marked_sync).
+// With `key` (info->encrypted) the version-5 file: the key block follows
+// the bitmap and the records hold what the keyed calls deliver, every
+// piece in max(size, 16) bytes.
 int write_delta_lz(OutFile* out, Bdev* src, Bdev* base,
-                   const std::vector<uint64_t>& bitmap, DeltaInfo* info,
+                   const std::vector<uint64_t>& bitmap,
+                   const std::vector<uint8_t>* key, DeltaInfo* info,
                    std::string* error) {
+  const uint32_t min_piece = info->encrypted ? 16 : 1;
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
   Header h = {info->block_size, info->granule,
               (info->full ? kDeltaFlagFull : 0) | kDeltaFlagLz |
-                  (info->dictionary ? kDeltaFlagDict : 0),
+                  (info->dictionary ? kDeltaFlagDict : 0) |
+                  (info->encrypted ? kDeltaFlagXts : 0),
               info->volume_bytes, info->n_granules, {0}};
   put_u64(h.owned, info->n_marked);
   put_u32(h.owned + 8, crc32c_sw(0, raw.data(), raw.size()));
-  int status = out->begin(info->dictionary ? kDeltaDict : kDeltaLz, h, error);
+  int status = out->begin(info->encrypted    ? kDeltaCts
+                          : info->dictionary ? kDeltaDict
+                                             : kDeltaLz,
+                          h, error);
   if (status != kIoOk) return status;
   VarRecordWriter writer(out, info->granule, record_granules(info->granule),
-                         info->n_marked);
-  if (out->write(raw.data(), raw.size())) {  // else end() reports it
+                         info->n_marked, min_piece);
+  uint8_t key_block[kKeyBlockBytes];
+  if (info->encrypted) put_key_block(key_block, xts_kcv(key->data()));
+  if (out->write(raw.data(), raw.size()) &&  // else end() reports it
+      (!info->encrypted || out->write(key_block, sizeof(key_block)))) {
     uint64_t packed = 0;
     std::string why;
-    const CompressSink sink = [&writer](const uint8_t* data,
-                                        const uint32_t* sizes, uint64_t,
-                                        uint64_t count) {
+    const CompressSink sink = [&writer, min_piece](const uint8_t* data,
+                                                   const uint32_t* sizes,
+                                                   uint64_t, uint64_t count) {
       int added = kIoOk;
       for (uint64_t i = 0; i < count && added == kIoOk; ++i) {
         added = writer.add(data, sizes[i]);
-        data += lz_padded(sizes[i]);
+        data += lz_padded(std::max(sizes[i], min_piece));
       }
       return added;
     };
+    const uint8_t* raw_key = info->encrypted ? key->data() : nullptr;
+    const size_t key_len = info->encrypted ? key->size() : 0;
     status = info->dictionary
                  ? bdev_dict_compress_marked_sync(src, 0, base, 0,
                                                   info->volume_bytes,
                                                   info->granule, bitmap, 0,
-                                                  sink, &packed, &why)
+                                                  sink, &packed, &why, raw_key,
+                                                  key_len, 0)
                  : bdev_compress_marked_sync(src, 0, info->volume_bytes,
                                              info->granule, bitmap, 0, sink,
-                                             &packed, &why);
+                                             &packed, &why, raw_key, key_len,
+                                             0);
     if (status != kIoOk || packed != info->n_marked || !writer.complete()) {
       if (why.empty()) {
         why = "reading the volume or writing " + out->tmp() + " failed";
@@ -244,7 +294,7 @@ int write_delta(OutFile* out, Bdev* src, Bdev* base,
                 const std::vector<uint8_t>* key, DeltaInfo* info,
                 std::string* error) {
   if (info->compressed) {
-    return write_delta_lz(out, src, base, bitmap, info, error);
+    return write_delta_lz(out, src, base, bitmap, key, info, error);
   }
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
@@ -529,21 +579,39 @@ int mark_all(Bdev* src, uint32_t granule, Marked* out, std::string* error) {
 // The record pass of a version-2 or version-4 import. dry_run validates
 // every piece here; otherwise bdev_decompress_marked_sync (version 4:
 // bdev_dict_decompress_marked_sync, whose dictionaries are the target's
-// granules) does, before it decodes.
-int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run, std::string* error) {
+// granules) does, before it decodes. A version-5 file's pieces are
+// ciphertext in max(size, 16) bytes each: dry_run checks records and sizes
+// and, given the key, decrypts and validates every piece; otherwise the
+// keyed calls validate, on the GPU while decoding or on the host.
+int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run,
+              const std::vector<uint8_t>* key, std::string* error) {
   const DeltaInfo& info = file->info;
+  const uint32_t min_piece = info.encrypted ? 16 : 1;
   VarRecordReader reader(&file->in, file->records_offset, file->record_area,
                          info.granule, record_granules(info.granule),
-                         info.n_marked);
+                         info.n_marked, min_piece);
   std::string why;
   int status = kIoOk;
   const uint8_t* piece = nullptr;
   uint32_t size = 0;
   if (dry_run) {
+    std::unique_ptr<XtsSchedules> keys;
+    if (info.encrypted && key != nullptr) {
+      keys.reset(new XtsSchedules(key->data()));
+    }
+    std::vector<uint8_t> plain(info.granule);
     for (uint64_t w = 0; w < file->bitmap.size() && status == kIoOk; ++w) {
       for (uint64_t word = file->bitmap[w]; word != 0 && status == kIoOk;
            word &= word - 1) {
         status = reader.next(&piece, &size, &why);
+        if (info.encrypted) {
+          if (keys == nullptr) continue;  // structure and CRCs only
+          if (status != kIoOk) break;
+          xts_decrypt_var(*keys,
+                          w * 64 + static_cast<uint64_t>(__builtin_ctzll(word)),
+                          piece, plain.data(), std::max(size, 16u));
+          piece = plain.data();
+        }
         std::string rule;
         if (status == kIoOk &&
             !(info.dictionary
@@ -566,19 +634,24 @@ int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run, std::string* error) {
         const int got = reader.next(&piece, &size, &why);
         if (got != kIoOk) return got;
         sizes[i] = size;
-        memcpy(data, piece, size);
-        memset(data + size, 0, lz_padded(size) - size);
-        data += lz_padded(size);
+        const uint32_t stored = std::max(size, min_piece);
+        memcpy(data, piece, stored);
+        memset(data + stored, 0, lz_padded(stored) - stored);
+        data += lz_padded(stored);
       }
       return static_cast<int>(kIoOk);
     };
+    const uint8_t* raw_key = info.encrypted ? key->data() : nullptr;
+    const size_t key_len = info.encrypted ? key->size() : 0;
     status = info.dictionary
                  ? bdev_dict_decompress_marked_sync(dst, 0, info.volume_bytes,
                                                     info.granule, file->bitmap,
-                                                    0, source, &applied, &why)
+                                                    0, source, &applied, &why,
+                                                    raw_key, key_len, 0)
                  : bdev_decompress_marked_sync(dst, 0, info.volume_bytes,
                                                info.granule, file->bitmap, 0,
-                                               source, &applied, &why);
+                                               source, &applied, &why, raw_key,
+                                               key_len, 0);
     if (status != kIoOk) {
       if (why.empty()) why = "writing the target failed";
       return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
@@ -606,11 +679,16 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
 int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
                       uint32_t granule, bool overwrite, DeltaMaps* maps,
                       DeltaInfo* stats, std::string* error, bool compress,
-                      const std::vector<uint8_t>* key, bool dictionary) {
+                      const std::vector<uint8_t>* key, bool dictionary,
+                      bool cts) {
   if (src == nullptr || path.empty()) {
     return fail(error, kIoInvalid, "bdev and path required");
   }
-  if (dictionary && (!compress || base == nullptr || key != nullptr)) {
+  if (cts && (key == nullptr || !compress)) {
+    return fail(error, kIoInvalid, "cts needs key and compress");
+  }
+  if (dictionary &&
+      (!compress || base == nullptr || (key != nullptr && !cts))) {
     return fail(error, kIoInvalid,
                 "dictionary needs compress and base (a clone), and no key");
   }
@@ -618,7 +696,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
     return fail(error, kIoInvalid,
                 "the key must be 64 bytes whose halves differ");
   }
-  if (key != nullptr && compress) {
+  if (key != nullptr && compress && !cts) {
     return fail(error, kIoInvalid, "key and compress exclude each other");
   }
   const std::string base_map = maps != nullptr ? maps->base_map : "";
@@ -666,7 +744,8 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
     return fail(error, kIoInvalid, "a key needs granule <= 16777216");
   }
   DeltaInfo info;
-  info.version = dictionary      ? kDeltaVersionDict
+  info.version = cts             ? kDeltaVersionCts
+                 : dictionary    ? kDeltaVersionDict
                  : compress      ? kDeltaVersionLz
                  : key != nullptr ? kDeltaVersionXts
                                   : kDeltaVersion;
@@ -760,7 +839,7 @@ int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
                     " is claimed; import runs offline only");
   }
   if (info.compressed) {
-    status = import_lz(dst, &file, dry_run, error);
+    status = import_lz(dst, &file, dry_run, key, error);
     if (status == kIoOk && stats != nullptr) *stats = info;
     return status;
   }

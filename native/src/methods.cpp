@@ -1309,7 +1309,8 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         // k_pack_marked, one launch per staging window; with "compress"
         // through k_lz_compress_marked and k_gather_var, with "dictionary"
         // too through k_lzd_compress_marked, with "key_file" through
-        // k_xts_pack_marked).
+        // k_xts_pack_marked; with "cts", "compress" and "key_file" through
+        // the compress kernels and k_xts_var).
         const std::string name = p.get_string("name");
         BdevPtr src = manager.find(name);
         if (!src) not_found("bdev " + name);
@@ -1341,7 +1342,8 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
             bdev_export_delta(src.get(), base.get(), path, granule,
                               p.get_bool("overwrite", false), &maps, &info,
                               &why, p.get_bool("compress", false), key.ptr(),
-                              p.get_bool("dictionary", false));
+                              p.get_bool("dictionary", false),
+                              p.get_bool("cts", false));
         if (status != kIoOk) throw delta_error("bdev_export_delta", status, why);
         JsonObject o;
         o["granule"] = Json(static_cast<int64_t>(info.granule));

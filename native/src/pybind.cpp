@@ -709,7 +709,7 @@ PYBIND11_MODULE(_hipstore, m) {
                                 bool compress, std::optional<py::bytes> key,
                                 std::optional<std::string> map_algorithm,
                                 std::optional<py::bytes> map_key,
-                                bool dictionary) {
+                                bool dictionary, bool cts) {
     DeltaInfo info;
     DeltaMaps maps;
     const KeyArg key_arg(key);
@@ -720,7 +720,8 @@ PYBIND11_MODULE(_hipstore, m) {
     delta_call("bdev_export_delta", [&](std::string* error) {
       return bdev_export_delta(src.get(), base ? base->get() : nullptr, path,
                                granule.value_or(0), overwrite, &maps, &info,
-                               error, compress, key_arg.ptr(), dictionary);
+                               error, compress, key_arg.ptr(), dictionary,
+                               cts);
     });
     py::dict d = delta_info_to_dict(info);
     if (!maps.map_out.empty()) d["map_bytes"] = maps.map_bytes;
@@ -730,7 +731,7 @@ PYBIND11_MODULE(_hipstore, m) {
      py::arg("base_map") = py::none(), py::arg("map_out") = py::none(),
      py::arg("compress") = false, py::arg("key") = py::none(),
      py::arg("map_algorithm") = py::none(), py::arg("map_key") = py::none(),
-     py::arg("dictionary") = false,
+     py::arg("dictionary") = false, py::arg("cts") = false,
      "Write the granules of src that differ from base, or from the state "
      "recorded in the fingerprint map base_map (every granule without "
      "either), to a hipstore delta file; map_out also writes the "
@@ -739,7 +740,9 @@ PYBIND11_MODULE(_hipstore, m) {
      "map_algorithm \"blake2s\" and map_key (32 bytes) make map_out an "
      "HSFP2 map (base_map decides by itself); dictionary (with compress "
      "and base) a version-4 file of HSLZD1 pieces, every granule "
-     "compressed against the same granule of base");
+     "compressed against the same granule of base; cts (with compress "
+     "and key, with or without dictionary) a version-5 file whose pieces "
+     "are HSXTS2 ciphertext (ciphertext stealing)");
 
   m.def("xts_encrypt_units", [](py::bytes data, uint32_t granule,
                                 py::bytes key, uint64_t first_unit) {
@@ -783,6 +786,36 @@ PYBIND11_MODULE(_hipstore, m) {
     return xts_kcv(reinterpret_cast<const uint8_t*>(raw_key.data()));
   }, py::arg("key"),
      "Key check value of an HSXTS1 key, as in a version-3 delta header");
+
+  // HSXTS2: one unit of any length >= 16 (ciphertext stealing).
+  const auto xts_var = [](const char* what, bool encrypt, py::bytes data,
+                          py::bytes key, uint64_t unit) {
+    const std::string in = data;
+    const std::string raw_key = key;
+    check_units(what, "", 16, raw_key);
+    if (in.size() < 16 || in.size() > kXtsMaxGranule) {
+      throw std::invalid_argument(std::string(what) +
+                                  ": 16 <= length <= 2^24");
+    }
+    const XtsSchedules keys(reinterpret_cast<const uint8_t*>(raw_key.data()));
+    std::string out(in.size(), '\0');
+    (encrypt ? xts_encrypt_var : xts_decrypt_var)(
+        keys, unit, reinterpret_cast<const uint8_t*>(in.data()),
+        reinterpret_cast<uint8_t*>(&out[0]), static_cast<uint32_t>(in.size()));
+    return py::bytes(out);
+  };
+  m.def("xts_encrypt_var", [xts_var](py::bytes data, py::bytes key,
+                                     uint64_t unit) {
+    return xts_var("xts_encrypt_var", true, data, key, unit);
+  }, py::arg("data"), py::arg("key"), py::arg("unit") = 0,
+     "HSXTS2-encrypt `data` (16 bytes or more, any length) as data unit "
+     "`unit` with ciphertext stealing (host codec, the byte model of "
+     "k_xts_var)");
+  m.def("xts_decrypt_var", [xts_var](py::bytes data, py::bytes key,
+                                     uint64_t unit) {
+    return xts_var("xts_decrypt_var", false, data, key, unit);
+  }, py::arg("data"), py::arg("key"), py::arg("unit") = 0,
+     "Inverse of xts_encrypt_var");
 
   m.def("bdev_xts_pack_marked", [](BdevPtr src, py::bytes bitmap,
                                    uint32_t granule, py::bytes key,
@@ -925,18 +958,25 @@ PYBIND11_MODULE(_hipstore, m) {
                                    std::optional<uint64_t> length,
                                    uint64_t staging_bytes,
                                    std::optional<BdevPtr> base,
-                                   uint64_t base_offset) {
+                                   uint64_t base_offset,
+                                   std::optional<py::bytes> key,
+                                   uint64_t first_unit) {
     const std::string raw = bitmap;
     const uint64_t len = marked_range("bdev_compress_marked", *src, src_offset,
                                       length, granule, raw);
     const std::vector<uint64_t> words = bitmap_words(raw);
+    const KeyArg key_arg(key);
     std::vector<uint32_t> sizes;
     std::string out;
     const CompressSink sink = [&](const uint8_t* data, const uint32_t* window,
                                   uint64_t, uint64_t count) {
       for (uint64_t i = 0; i < count; ++i) {
-        out.append(reinterpret_cast<const char*>(data), window[i]);
-        data += lz_padded(window[i]);
+        // Keyed: the piece as it lies in the stream, pad included.
+        const uint64_t room =
+            lz_padded(key_arg.given ? std::max(window[i], 16u) : window[i]);
+        out.append(reinterpret_cast<const char*>(data),
+                   key_arg.given ? room : window[i]);
+        data += room;
       }
       sizes.insert(sizes.end(), window, window + count);
       return 0;
@@ -944,36 +984,53 @@ PYBIND11_MODULE(_hipstore, m) {
     delta_call("bdev_compress_marked", [&](std::string* error) {
       return base ? bdev_dict_compress_marked_sync(
                         src.get(), src_offset, base->get(), base_offset, len,
-                        granule, words, staging_bytes, sink, nullptr, error)
-                  : bdev_compress_marked_sync(src.get(), src_offset, len,
-                                              granule, words, staging_bytes,
-                                              sink, nullptr, error);
+                        granule, words, staging_bytes, sink, nullptr, error,
+                        key_arg.given ? key_arg.bytes.data() : nullptr,
+                        key_arg.bytes.size(), first_unit)
+                  : bdev_compress_marked_sync(
+                        src.get(), src_offset, len, granule, words,
+                        staging_bytes, sink, nullptr, error,
+                        key_arg.given ? key_arg.bytes.data() : nullptr,
+                        key_arg.bytes.size(), first_unit);
     });
     return py::make_tuple(sizes, py::bytes(out));
   }, py::arg("src"), py::arg("bitmap"), py::arg("granule"),
      py::arg("src_offset") = 0, py::arg("length") = py::none(),
      py::arg("staging_bytes") = 0, py::arg("base") = py::none(),
-     py::arg("base_offset") = 0,
+     py::arg("base_offset") = 0, py::arg("key") = py::none(),
+     py::arg("first_unit") = 0,
      "Compress the granules marked in `bitmap`, ascending (on-GPU for HBM "
      "bdevs): (stored sizes, the pieces back to back). With `base`, every "
      "granule is compressed against the same granule of the range of "
-     "`base` at base_offset (HSLZD1)");
+     "`base` at base_offset (HSLZD1). With `key` (64 bytes) every piece is "
+     "HSXTS2 ciphertext of unit first_unit + its granule's index "
+     "(k_xts_var for HBM bdevs) and the second item is the stream as "
+     "stored: piece i, padded with zeros to a multiple of 16 and to at "
+     "least 16 bytes, after the padded pieces before it");
 
   m.def("bdev_decompress_marked", [](BdevPtr dst, py::bytes bitmap,
                                      uint32_t granule,
                                      std::vector<uint32_t> sizes,
                                      py::bytes data, uint64_t dst_offset,
                                      std::optional<uint64_t> length,
-                                     uint64_t staging_bytes, bool dictionary) {
+                                     uint64_t staging_bytes, bool dictionary,
+                                     std::optional<py::bytes> key,
+                                     uint64_t first_unit) {
     const std::string raw = bitmap;
     const uint64_t len = marked_range("bdev_decompress_marked", *dst,
                                       dst_offset, length, granule, raw);
     const std::vector<uint64_t> words = bitmap_words(raw);
+    const KeyArg key_arg(key);
     const std::string pieces = data;
+    // What piece i takes of `data`: its bytes, or with a key its padded
+    // room in the stream.
+    const auto room = [&](uint32_t size) -> uint64_t {
+      return key_arg.given ? lz_padded(std::max(size, 16u)) : size;
+    };
     // Where each piece starts; sizes that overrun `data` fail below.
     std::vector<uint64_t> starts(sizes.size() + 1, 0);
     for (size_t i = 0; i < sizes.size(); ++i) {
-      starts[i + 1] = starts[i] + sizes[i];
+      starts[i + 1] = starts[i] + room(sizes[i]);
     }
     if (starts.back() != pieces.size()) {
       throw std::invalid_argument(
@@ -987,30 +1044,40 @@ PYBIND11_MODULE(_hipstore, m) {
         const uint32_t size = sizes[first_rank + i];
         window[i] = size;
         if (size == 0 || size > granule) continue;  // refused after us
-        memcpy(out, pieces.data() + starts[first_rank + i], size);
-        memset(out + size, 0, lz_padded(size) - size);
-        out += lz_padded(size);
+        const uint64_t have = room(size);
+        const uint64_t take = lz_padded(have);
+        memcpy(out, pieces.data() + starts[first_rank + i], have);
+        memset(out + have, 0, take - have);
+        out += take;
       }
       return 0;
     };
+    const uint8_t* key_ptr = key_arg.given ? key_arg.bytes.data() : nullptr;
     delta_call("bdev_decompress_marked", [&](std::string* error) {
       return dictionary
                  ? bdev_dict_decompress_marked_sync(dst.get(), dst_offset, len,
                                                     granule, words,
                                                     staging_bytes, source,
-                                                    &unpacked, error)
+                                                    &unpacked, error, key_ptr,
+                                                    key_arg.bytes.size(),
+                                                    first_unit)
                  : bdev_decompress_marked_sync(dst.get(), dst_offset, len,
                                                granule, words, staging_bytes,
-                                               source, &unpacked, error);
+                                               source, &unpacked, error,
+                                               key_ptr, key_arg.bytes.size(),
+                                               first_unit);
     });
     return unpacked;
   }, py::arg("dst"), py::arg("bitmap"), py::arg("granule"), py::arg("sizes"),
      py::arg("data"), py::arg("dst_offset") = 0, py::arg("length") = py::none(),
      py::arg("staging_bytes") = 0, py::arg("dictionary") = false,
+     py::arg("key") = py::none(), py::arg("first_unit") = 0,
      "Decode the pieces of bdev_compress_marked into the granules marked in "
      "`bitmap`; every piece is validated on the host first. Returns the "
      "number written. `dictionary`: the pieces are HSLZD1 and the "
-     "dictionary of a granule is what `dst` holds there before the call");
+     "dictionary of a granule is what `dst` holds there before the call. "
+     "With `key`, `data` is the keyed stream of bdev_compress_marked; HBM "
+     "bdevs decrypt it on the GPU (k_xts_var) and validate while decoding");
 
   m.def("xts_marked_probe", [](BdevPtr bdev, py::bytes bitmap,
                                uint32_t granule, py::bytes key, bool unpack,

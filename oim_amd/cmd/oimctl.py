@@ -90,6 +90,10 @@ def main(argv=None) -> int:
                              help="with --compress and --base: compress "
                              "every granule against the base's (restore "
                              "onto a volume at the base state, once)")
+            cmd.add_argument("--cts", action="store_true",
+                             help="with --compress and --key-file: encrypt "
+                             "the compressed pieces (ciphertext stealing; "
+                             "a version-5 file)")
         if name in ("checkpoint", "restore"):
             cmd.add_argument("--key-file", default="",
                              help="file of 64 raw bytes on the data-path "
@@ -194,7 +198,7 @@ def main(argv=None) -> int:
                         compress=args.compress, key_file=args.key_file,
                         map_algorithm=args.map_algorithm,
                         map_key_file=args.map_key_file,
-                        dictionary=args.dictionary),
+                        dictionary=args.dictionary, cts=args.cts),
                     metadata=metadata, timeout=600)
                 print(f"checkpointed {args.volume} -> {args.path}: "
                       f"{reply.saved} of {reply.granules} granules, "

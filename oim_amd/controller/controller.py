@@ -422,7 +422,8 @@ class Controller(spec.ControllerServicer):
                         key_file=request.key_file or None,
                         map_algorithm=request.map_algorithm or None,
                         map_key_file=request.map_key_file or None,
-                        dictionary=request.dictionary)
+                        dictionary=request.dictionary,
+                        cts=request.cts)
                 except hipstore.RpcError as err:
                     self._abort_delta(context, err)
         return spec.CheckpointMallocBDevReply(

@@ -350,7 +350,8 @@ def bdev_export_delta(client: Client, name: str, path: str,
                       key_file: Optional[str] = None,
                       map_algorithm: Optional[str] = None,
                       map_key_file: Optional[str] = None,
-                      dictionary: bool = False) -> Dict:
+                      dictionary: bool = False,
+                      cts: bool = False) -> Dict:
     """Checkpoint a volume to a delta file: every granule, or with
     `base` (an earlier clone) or `base_map` (the fingerprint map written
     with an earlier checkpoint; no clone needed) only the granules that
@@ -370,6 +371,10 @@ def bdev_export_delta(client: Client, name: str, path: str,
     same granule of `base` (a version-4 file): an in-place edit of a
     granule then costs a few dozen bytes whatever the content. Such a
     file must be imported onto a volume that is at the base state, once.
+    `cts` (only with `compress` and `key_file`, with or without
+    `dictionary`) stores every compressed piece encrypted with ciphertext
+    stealing (a version-5 file, which older readers refuse): small and
+    never in the clear outside device memory.
 
     Returns {granule, granules, saved, file_bytes, full}, with map_out
     also map_bytes and with compress stored_bytes (the bytes the granules
@@ -392,6 +397,8 @@ def bdev_export_delta(client: Client, name: str, path: str,
         params["key_file"] = key_file
     if dictionary:
         params["dictionary"] = True
+    if cts:
+        params["cts"] = True
     _map_params(params, map_algorithm, map_key_file)
     return client.invoke("bdev_export_delta", params)
 
@@ -400,7 +407,8 @@ def bdev_import_delta(client: Client, name: str, path: str,
                       dry_run: bool = False,
                       key_file: Optional[str] = None) -> Dict:
     """Apply a delta file to an unclaimed volume; dry_run checks the
-    file (every CRC) and writes nothing. An encrypted (version-3) file
+    file (every CRC) and writes nothing. An encrypted (version-3 or
+    version-5) file
     needs the `key_file` it was written with; a wrong key is refused
     before anything is written, and dry_run works without a key.
 

@@ -78,7 +78,7 @@ MESSAGES = [
              Field("compress", 7, "bool"), Field("key_file", 8, "string"),
              Field("map_algorithm", 9, "string"),
              Field("map_key_file", 10, "string"),
-             Field("dictionary", 11, "bool")]),
+             Field("dictionary", 11, "bool"), Field("cts", 12, "bool")]),
     Message("CheckpointMallocBDevReply",
             [Field("granules", 1, "int64"), Field("saved", 2, "int64"),
              Field("file_bytes", 3, "int64")]),

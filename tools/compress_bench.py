@@ -23,7 +23,14 @@ granules by a 64-byte in-place edit, and per round an export against the
 base as a version-1, a version-2 (compress) and a version-4 (compress,
 dictionary) file, each imported onto a third volume that was put back to
 the base state first (untimed). One JSON line per content with the
-times, the file sizes and the stored ratios of the changed granules."""
+times, the file sizes and the stored ratios of the changed granules.
+
+    python tools/compress_bench.py --cts ...
+
+adds a third export and import per round to the full-volume run: compress
+with a key and cts (a version-5 file, keys "export_cts", "import_cts"),
+alternating with the other two, so the cost of encrypting the pieces
+reads off one line."""
 import argparse
 import json
 import os
@@ -38,6 +45,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oim_amd._hipstore as hs  # noqa: E402
 
 STEP = 64 << 20
+KEY = bytes(range(1, 65))  # for --cts
 
 
 def content_chunks(kind, length, rng):
@@ -133,6 +141,8 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dictionary", action="store_true",
                     help="measure an incremental as version 1, 2 and 4")
+    ap.add_argument("--cts", action="store_true",
+                    help="also measure compress with a key and cts")
     ap.add_argument("--changed", type=float, default=0.01,
                     help="with --dictionary: share of granules edited")
     args = ap.parse_args()
@@ -149,6 +159,8 @@ def main():
         return incremental(args, length, live, back)
     path = os.path.join(args.dir, f"lzbench-{os.getpid()}.delta")
     modes = [False] if args.no_compress else [False, True]
+    if args.cts:
+        modes.append("cts")
 
     for kind in args.contents:
         rng = np.random.default_rng(20264)
@@ -165,16 +177,20 @@ def main():
                 if os.path.exists(path):
                     os.unlink(path)  # never two copies in the tmpfs
                 kwargs = {"compress": True} if lz else {}
+                if lz == "cts":
+                    kwargs.update(key=KEY, cts=True)
                 t0 = time.perf_counter()
                 info = hs.bdev_export_delta(live, path, granule=args.granule,
                                             **kwargs)
                 t1 = time.perf_counter()
-                hs.bdev_import_delta(back, path)
+                hs.bdev_import_delta(back, path, key=kwargs.get("key"))
                 t2 = time.perf_counter()
                 if run > 0:
                     samples[("export", lz)].append(t1 - t0)
                     samples[("import", lz)].append(t2 - t1)
-                if lz:
+                if lz == "cts":
+                    out["file_bytes_cts"] = info["file_bytes"]
+                elif lz:
                     out["file_bytes_lz"] = info["file_bytes"]
                     out["ratio"] = round(length / info["stored_bytes"], 3)
                 else:
@@ -183,7 +199,8 @@ def main():
             sys.exit(f"compress_bench: {kind}: restored volume differs")
         os.unlink(path)
         for (what, lz), values in samples.items():
-            out[what + ("_lz" if lz else "")] = summary(values, length)
+            out[what + ("_cts" if lz == "cts" else "_lz" if lz else "")] = \
+                summary(values, length)
         print(json.dumps(out), flush=True)
 
 
