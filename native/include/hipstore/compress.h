@@ -52,7 +52,7 @@
 //   - winner, inserts, extension (while q + length < 2G - 5), emission
 //     and final literals are HSLZ1's with 2G for G; literal lengths and
 //     the stored-size bound are relative to G (the output is X alone).
-// lz_dict_compress_granule and k_lzd_compress_marked emit identical
+// lz_dict_compress_granule and k_lz_compress_marked<true> emit identical
 // bytes.
 
 #pragma once
@@ -63,6 +63,7 @@
 #include <vector>
 
 #include "hipstore/bdev.h"
+#include "hipstore/crypt.h"
 
 namespace hipstore {
 
@@ -116,6 +117,20 @@ bool lz_dict_decompress_granule(const uint8_t* piece, uint64_t size,
                                 uint32_t granule, const uint8_t* dict,
                                 uint8_t* out, std::string* why = nullptr);
 
+// What the two marked calls below take besides their range.
+struct LzOptions {
+  // As bdev_pack_marked_sync's: 0 for the default, else at least a granule.
+  uint64_t staging_bytes = 0;
+  // Set (key or len) for a keyed call, see below.
+  XtsKey key;
+  // HSLZD1, compress: granule g of the range is compressed against
+  // granule g of the range of `base` at base_offset. Null for HSLZ1.
+  Bdev* base = nullptr;
+  uint64_t base_offset = 0;
+  // HSLZD1, decompress: the target is its own dictionary.
+  bool dictionary = false;
+};
+
 // bdev_pack_marked_sync with every granule compressed: sink(data, sizes,
 // first_rank, count) receives the stored sizes of marked granules
 // first_rank .. first_rank + count - 1 and their pieces in `data`, piece
@@ -126,17 +141,24 @@ bool lz_dict_decompress_granule(const uint8_t* piece, uint64_t size,
 // cross PCIe; every other bdev goes through bdev_pack_marked_sync's
 // generic path and lz_compress_granule. Both paths hand the sink the
 // same chunks and the same bytes.
+//
+// With options.base (HSLZD1): `base` has the same block size and both
+// ranges are valid. The kernel path (k_lz_compress_marked<true>) applies
+// when both bdevs are HBM-resident and reachable from one device, as for
+// bdev_diff_sync; otherwise both are read through the bdev interface in
+// spans of at most 1 MiB and lz_dict_compress_granule does the work. Same
+// chunks and bytes on both paths. Ranges that overlap in one backing
+// store are kIoInvalid, as in bdev_copy_marked_sync.
 using CompressSink = std::function<int(const uint8_t* data,
                                        const uint32_t* sizes,
                                        uint64_t first_rank, uint64_t count)>;
 int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               uint32_t granule,
                               const std::vector<uint64_t>& bitmap,
-                              uint64_t staging_bytes, const CompressSink& sink,
+                              const LzOptions& options,
+                              const CompressSink& sink,
                               uint64_t* packed = nullptr,
-                              std::string* error = nullptr,
-                              const uint8_t* key = nullptr, size_t key_len = 0,
-                              uint64_t first_unit = 0);
+                              std::string* error = nullptr);
 
 // The inverse: source(data, sizes, first_rank, count) fills the stored
 // sizes and the pieces of the next chunk in the layout above (`data` has
@@ -146,22 +168,26 @@ int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
 // Chunks delivered before it stay written. HBM bdevs decode in
 // k_lz_decompress_marked, which bounds every index on its own and
 // reports a piece it had to give up in a per-window flag array: such a
-// piece is kIoFailed.
+// piece is kIoFailed. options.base is not used.
+//
+// With options.dictionary (HSLZD1): the dictionary of a granule is what
+// the target holds there when the call reaches it, so the target must be
+// at the base state and the call is not idempotent. Pieces are checked
+// with lz_dict_validate_granule first. k_lz_decompress_marked<true, ...>
+// reads a granule into LDS before it overwrites it and touches no other.
 using DecompressSource = std::function<int(uint8_t* data, uint32_t* sizes,
                                            uint64_t first_rank,
                                            uint64_t count)>;
 int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 uint64_t length, uint32_t granule,
                                 const std::vector<uint64_t>& bitmap,
-                                uint64_t staging_bytes,
+                                const LzOptions& options,
                                 const DecompressSource& source,
                                 uint64_t* unpacked = nullptr,
-                                std::string* error = nullptr,
-                                const uint8_t* key = nullptr,
-                                size_t key_len = 0, uint64_t first_unit = 0);
+                                std::string* error = nullptr);
 
-// Keyed calls. All four calls take an optional key (the 64 bytes of
-// crypt.h) and a first unit number: every piece is then one HSXTS2 unit
+// Keyed calls. With options.key (the 64 bytes of crypt.h and a first unit
+// number), with or without a dictionary, every piece is one HSXTS2 unit
 // whose number is first_unit + the granule's index in the range, and only
 // ciphertext reaches the sink or comes from the source. `sizes` stay the
 // true stored sizes; piece i sits at the sum of lz_padded(max(sizes[j],
@@ -180,41 +206,5 @@ int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
 //   every other bdev: xts_encrypt_var / xts_decrypt_var on the host, then
 //     the host validators as without a key. Both paths hand over the same
 //     chunks and bytes and refuse the same pieces.
-
-// bdev_compress_marked_sync with HSLZD1: granule g of the range of `src`
-// is compressed against granule g of the range of `base` (same block
-// size, both ranges valid). The kernel path (k_lzd_compress_marked)
-// applies when both are HBM-resident and reachable from one device, as
-// for bdev_diff_sync; otherwise both are read through the bdev interface
-// in spans of at most 1 MiB and lz_dict_compress_granule does the work.
-// Same chunks and bytes on both paths. Ranges that overlap in one
-// backing store are kIoInvalid, as in bdev_copy_marked_sync.
-int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
-                                   uint64_t base_offset, uint64_t length,
-                                   uint32_t granule,
-                                   const std::vector<uint64_t>& bitmap,
-                                   uint64_t staging_bytes,
-                                   const CompressSink& sink,
-                                   uint64_t* packed = nullptr,
-                                   std::string* error = nullptr,
-                                   const uint8_t* key = nullptr,
-                                   size_t key_len = 0,
-                                   uint64_t first_unit = 0);
-
-// bdev_decompress_marked_sync with HSLZD1: the dictionary of a granule is
-// what the target holds there when the call reaches it, so the target
-// must be at the base state and the call is not idempotent. Pieces are
-// checked with lz_dict_validate_granule first. k_lzd_decompress_marked
-// reads a granule into LDS before it overwrites it and touches no other.
-int bdev_dict_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
-                                     uint64_t length, uint32_t granule,
-                                     const std::vector<uint64_t>& bitmap,
-                                     uint64_t staging_bytes,
-                                     const DecompressSource& source,
-                                     uint64_t* unpacked = nullptr,
-                                     std::string* error = nullptr,
-                                     const uint8_t* key = nullptr,
-                                     size_t key_len = 0,
-                                     uint64_t first_unit = 0);
 
 }  // namespace hipstore

@@ -103,6 +103,15 @@ void xts_decrypt_var(const XtsSchedules& keys, uint64_t unit,
 // xts_key_ok(key) required.
 uint32_t xts_kcv(const uint8_t key[kXtsKeyBytes]);
 
+// The key argument of the marked calls here and in compress.h: `len`
+// bytes at `key` (not owned), and the unit number of granule 0 of the
+// call's range.
+struct XtsKey {
+  const uint8_t* key = nullptr;
+  size_t len = 0;
+  uint64_t first_unit = 0;
+};
+
 // bdev_pack_marked_sync with every granule encrypted: validation, plan,
 // windows, staging and the chunks handed to the sink are the same; also
 // kIoInvalid unless xts_key_ok, xts_granule_ok and first_unit + the
@@ -115,8 +124,7 @@ uint32_t xts_kcv(const uint8_t key[kXtsKeyBytes]);
 int bdev_xts_pack_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               uint32_t granule,
                               const std::vector<uint64_t>& bitmap,
-                              const uint8_t* key, size_t key_len,
-                              uint64_t first_unit, uint64_t staging_bytes,
+                              const XtsKey& key, uint64_t staging_bytes,
                               const PackSink& sink, uint64_t* packed = nullptr);
 
 // The inverse: source fills the next chunk with ciphertext, which is
@@ -126,8 +134,7 @@ int bdev_xts_pack_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
 int bdev_xts_unpack_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 uint64_t length, uint32_t granule,
                                 const std::vector<uint64_t>& bitmap,
-                                const uint8_t* key, size_t key_len,
-                                uint64_t first_unit, uint64_t staging_bytes,
+                                const XtsKey& key, uint64_t staging_bytes,
                                 const UnpackSource& source,
                                 uint64_t* unpacked = nullptr);
 

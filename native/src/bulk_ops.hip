@@ -785,88 +785,57 @@ void wait_marked_event(hipEvent_t event) {
   HIP_CHECK(err);
 }
 
-namespace {
-
-// What both GPU window loops run on. One stream and one event per
-// staging half: launch window k+1, then wait for window k only. The
-// kernels read the plan and fill or drain the two halves in place, so
-// the device's view of those is kept here too.
-struct MarkedStream : HalvesStream {
-  uint32_t granule;
-  uint64_t half_bytes;
-  uint8_t* staging;
-  uint8_t* dev_staging;
-  const unsigned long long* dev_words;
-  const uint32_t* dev_ranks;
-  uint8_t* base;  // the bdev's range in device memory
-
-  MarkedStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
-               const MarkedPlan& plan)
-      : HalvesStream(device), granule(granule_bytes),
-        half_bytes(plan.chunk_granules * granule_bytes),
-        staging(bulk_ctx().staging.reserve(2 * half_bytes)),
-        dev_staging(device_view(staging)), dev_words(device_view(plan.words)),
-        dev_ranks(device_view(plan.ranks)),
-        base(static_cast<uint8_t*>(bdev->device_base()) + offset) {}
-
-  // k_pack_marked or k_unpack_marked over one window and one half.
-  template <typename Kernel>
-  void launch(Kernel kernel, const MarkedWindow& win, int half) {
-    hipLaunchKernelGGL(kernel, dim3(marked_window_grid(win)),
-                       dim3(kWavesPerWg * 64), 0, stream, base,
-                       dev_staging + half * half_bytes, dev_words, dev_ranks,
-                       win, granule);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(done[half], stream));
+int plan_marked_windows(Bdev* bdev, uint64_t offset, uint64_t length,
+                        uint32_t granule, const std::vector<uint64_t>& bitmap,
+                        uint64_t staging_bytes, bool have_callback,
+                        MarkedPlan* plan) {
+  if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule,
+                         &bitmap) ||
+      (staging_bytes != 0 && staging_bytes < granule)) {
+    return kIoInvalid;
   }
-};
-
-// Pack launches one window ahead, then waits for the current one.
-int marked_gpu(MarkedStream& ms, const MarkedPlan& plan, const PackSink& sink,
-               uint64_t* packed) {
-  MarkedWindow cur = next_marked_window(plan, 0, 0);
-  ms.launch(k_pack_marked, cur, 0);
-  for (int half = 0;; half ^= 1) {
-    const uint64_t next_rank = cur.first_rank + static_cast<uint64_t>(cur.count);
-    MarkedWindow next{};
-    if (next_rank < plan.marked) {
-      next = next_marked_window(plan, cur.g_end, next_rank);
-      ms.launch(k_pack_marked, next, half ^ 1);
-    }
-    wait_marked_event(ms.done[half]);
-    const int status =
-        sink(ms.staging + half * ms.half_bytes, cur.first_rank, cur.count);
-    if (status != 0) return status;
-    *packed = next_rank;
-    if (next_rank >= plan.marked) return kIoOk;
-    cur = next;
-  }
+  *plan = build_marked_plan(length / granule, bitmap, true);
+  if (plan->marked == 0) return kIoOk;
+  if (!have_callback) return kIoInvalid;
+  const uint64_t half =
+      staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
+  plan->chunk_granules =
+      std::min(std::max<uint64_t>(1, half / granule), plan->marked);
+  return kIoOk;
 }
 
-int marked_gpu(MarkedStream& ms, const MarkedPlan& plan,
+namespace {
+
+// k_pack_marked per window on the shared pack loop; the sink sees one
+// staging half at a time.
+int marked_gpu(WindowStream& ws, const MarkedPlan& plan, const PackSink& sink,
+               uint64_t* packed) {
+  return pack_windows(
+      ws, plan,
+      [&](const MarkedWindow& win, int half) {
+        ws.launch(k_pack_marked, marked_window_grid(win), kWavesPerWg * 64,
+                  win, half);
+      },
+      [](const MarkedWindow&, int) {},
+      [&](const MarkedWindow& win, int half) {
+        return sink(ws.half_of(half), win.first_rank, win.count);
+      },
+      packed);
+}
+
+// k_unpack_marked likewise, the source filling a half before its launch.
+int marked_gpu(WindowStream& ws, const MarkedPlan& plan,
                const UnpackSource& source, uint64_t* unpacked) {
-  bool used[2] = {false, false};
-  uint64_t g_begin = 0;
-  uint64_t launched = 0;
-  for (int half = 0; launched < plan.marked; half ^= 1) {
-    const MarkedWindow win = next_marked_window(plan, g_begin, launched);
-    // The kernel two windows back read this half: let it finish first.
-    if (used[half]) wait_marked_event(ms.done[half]);
-    const int status =
-        source(ms.staging + half * ms.half_bytes, win.first_rank, win.count);
-    if (status != 0) {
-      HIP_CHECK(hipStreamSynchronize(ms.stream));
-      *unpacked = launched;
-      return status;
-    }
-    ms.launch(k_unpack_marked, win, half);
-    used[half] = true;
-    launched += win.count;
-    g_begin = win.g_end;
-  }
-  HIP_CHECK(hipStreamSynchronize(ms.stream));
-  *unpacked = launched;
-  return kIoOk;
+  return unpack_windows(
+      ws, plan, [](int) { return 0; },
+      [&](const MarkedWindow& win, int half) {
+        return source(ws.half_of(half), win.first_rank, win.count);
+      },
+      [&](const MarkedWindow& win, int half) {
+        ws.launch(k_unpack_marked, marked_window_grid(win), kWavesPerWg * 64,
+                  win, half);
+      },
+      unpacked);
 }
 
 // Generic path: the same chunks, filled from (or drained to) runs of
@@ -919,32 +888,21 @@ int marked_stream_sync(Bdev* bdev, uint64_t offset, uint64_t length,
                        uint32_t granule, const std::vector<uint64_t>& bitmap,
                        uint64_t staging_bytes, const Chunk& chunk,
                        uint64_t* moved_out) {
-  uint64_t unused = 0;
-  uint64_t* moved = moved_out != nullptr ? moved_out : &unused;
-  *moved = 0;
-  try {
-    if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule,
-                           &bitmap) ||
-        (staging_bytes != 0 && staging_bytes < granule)) {
-      return kIoInvalid;
-    }
-    MarkedPlan plan = build_marked_plan(length / granule, bitmap, true);
-    if (plan.marked == 0) return kIoOk;
-    if (!chunk) return kIoInvalid;
-    const uint64_t half =
-        staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
-    plan.chunk_granules =
-        std::min(std::max<uint64_t>(1, half / granule), plan.marked);
+  return marked_call(moved_out, [&](uint64_t* moved) -> int {
+    MarkedPlan plan;
+    const int status =
+        plan_marked_windows(bdev, offset, length, granule, bitmap,
+                            staging_bytes, static_cast<bool>(chunk), &plan);
+    if (status != kIoOk || plan.marked == 0) return status;
     const int device = granule_kernel_device(bdev, bdev);
     if (device >= 0) {
-      MarkedStream ms(device, bdev, offset, granule, plan);
-      return marked_gpu(ms, plan, chunk, moved);
+      WindowStream ws(device, bdev, offset, granule, plan,
+                      bulk_ctx().staging);
+      return marked_gpu(ws, plan, chunk, moved);
     }
     return marked_generic(bdev, offset, granule, plan,
                           std::is_same<Chunk, PackSink>::value, chunk, moved);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
+  });
 }
 
 }  // namespace
@@ -1067,15 +1025,12 @@ int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
                           uint32_t granule, uint64_t staging_bytes,
                           const FingerprintSink& sink, uint64_t* done_out,
                           const FingerprintKind& kind) {
-  uint64_t unused = 0;
-  uint64_t* done = done_out != nullptr ? done_out : &unused;
-  *done = 0;
   // The midstate is key-equivalent: cleared on every way out.
   struct Start {
     Blake2sMidstate mid;
     ~Start() { explicit_bzero(&mid, sizeof(mid)); }
   } start;
-  try {
+  return marked_call(done_out, [&](uint64_t* done) -> int {
     if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule) ||
         (staging_bytes != 0 && staging_bytes < 2 * kFingerprintBytes) ||
         !sink || !fingerprint_kind_ok(kind)) {
@@ -1101,9 +1056,7 @@ int bdev_fingerprint_sync(Bdev* bdev, uint64_t offset, uint64_t length,
     GranuleHasher hasher;
     return fingerprint_generic(bdev, offset, n_granules, granule, window,
                                hasher, sink, done);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
+  });
 }
 
 // Measurement aid (tools/delta_bench.py): times, on the host clock from

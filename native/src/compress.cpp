@@ -1,6 +1,6 @@
 // The HSLZ1 and HSLZD1 granule codecs on the host (hipstore/compress.h):
-// the normative parse, byte for byte what k_lz_compress_marked and
-// k_lzd_compress_marked emit, the validator and the decoder. Plain host
+// the normative parse, byte for byte what k_lz_compress_marked<false> and
+// k_lz_compress_marked<true> emit, the validator and the decoder. Plain host
 // code; the marked calls and the kernels are in compress_ops.hip.
 
 #include "hipstore/compress.h"

@@ -23,7 +23,7 @@
 // waves that fit 64 KiB: compress 4 waves up to G = 4096 (64 KiB at
 // 4096), 2 up to 12288, 1 above; decompress 4 up to 8192, 2 above.
 //
-// HSLZD1 (k_lzd_compress_marked, k_lzd_decompress_marked): the same split
+// HSLZD1 (the kDict instantiations of the two kernels): the same split
 // and movement with the base granule as dictionary. Compress holds the
 // image D || X, the block and the table, 3 * G + 8 KiB per wave: D comes
 // from the base volume, the table is seeded from it, and the scan runs
@@ -206,55 +206,18 @@ __device__ __forceinline__ uint32_t lz_parse(const uint8_t* in, uint8_t* out,
 // Scratch slot `slot` (stride G) receives the piece, its pad up to the
 // next multiple of 16 zeroed, and sizes[slot] its stored size: plain
 // loads and stores, no global atomics, nothing read that an earlier
-// launch left in scratch or sizes.
+// launch left in scratch or sizes. Per-wave LDS: the granule X (G), the
+// block (G) and the table.
+//
+// kDict is HSLZD1: granule g of `base` is the dictionary D of granule g
+// of `src` (`base` is not read without it). The per-wave LDS then begins
+// with D, the image D || X (2G, D immediately before X, so a u32 that
+// straddles the boundary and a match that runs from D into X are plain
+// addressing), and the cleared table is seeded with the positions of D in
+// rows of 64: atomicMax of position + 1 leaves the greatest position in a
+// slot whatever the order.
+template <bool kDict>
 __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_compress_marked(
-    const uint8_t* __restrict__ src, uint8_t* __restrict__ scratch,
-    uint32_t* __restrict__ sizes, const unsigned long long* __restrict__ bitmap,
-    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
-    uint32_t granule) {
-  extern __shared__ uint4 lz_lds[];
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n16 = granule >> 4;
-  uint8_t* in = reinterpret_cast<uint8_t*>(lz_lds) +
-                (threadIdx.x >> 6) * (2 * granule + kLzTableBytes);
-  uint8_t* out = in + granule;
-  uint32_t* table = reinterpret_cast<uint32_t*>(out + granule);
-  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
-                                                      uint32_t slot) {
-    const uint4* __restrict__ pg =
-        reinterpret_cast<const uint4*>(src + g * granule);
-    uint4* in16 = reinterpret_cast<uint4*>(in);
-    uint4* table16 = reinterpret_cast<uint4*>(table);
-#pragma unroll 4
-    for (uint32_t i = lane; i < n16; i += 64) in16[i] = pg[i];
-    for (uint32_t i = lane; i < kLzTableBytes / 16; i += 64) {
-      table16[i] = make_uint4(0, 0, 0, 0);
-    }
-    wave_sync();
-    const uint32_t size = lz_parse<false>(in, out, table, granule, lane);
-    // size < granule and granule % 16 == 0: the pad stays inside `out`.
-    if (size != granule && lane < ((16 - (size & 15)) & 15)) {
-      out[size + lane] = 0;
-    }
-    wave_sync();
-    const uint4* from =
-        size == granule ? in16 : reinterpret_cast<const uint4*>(out);
-    uint4* __restrict__ ps = reinterpret_cast<uint4*>(
-        scratch + static_cast<uint64_t>(slot) * granule);
-    for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) ps[i] = from[i];
-    if (lane == 0) sizes[slot] = size;
-    wave_sync();  // the next granule overwrites this LDS
-  });
-}
-
-// k_lz_compress_marked with HSLZD1: granule g of `base` is the
-// dictionary of granule g of `src`. Per-wave LDS: the image D || X (2G,
-// D immediately before X, so a u32 that straddles the boundary and a
-// match that runs from D into X are plain addressing), the block (G) and
-// the table. The table is cleared, then seeded with the positions of D
-// in rows of 64: atomicMax of position + 1 leaves the greatest position
-// in a slot whatever the order. Slots, pad and sizes as above.
-__global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_compress_marked(
     const uint8_t* __restrict__ src, const uint8_t* __restrict__ base,
     uint8_t* __restrict__ scratch, uint32_t* __restrict__ sizes,
     const unsigned long long* __restrict__ bitmap,
@@ -264,40 +227,44 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_compress_marked(
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t n16 = granule >> 4;
   uint8_t* image = reinterpret_cast<uint8_t*>(lz_lds) +
-                   (threadIdx.x >> 6) * (3 * granule + kLzTableBytes);
-  uint8_t* out = image + 2 * granule;
+                   (threadIdx.x >> 6) *
+                       ((kDict ? 3 : 2) * granule + kLzTableBytes);
+  uint8_t* out = image + (kDict ? 2 : 1) * granule;
   uint32_t* table = reinterpret_cast<uint32_t*>(out + granule);
   wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
                                                       uint32_t slot) {
     const uint4* __restrict__ pd =
-        reinterpret_cast<const uint4*>(base + g * granule);
+        kDict ? reinterpret_cast<const uint4*>(base + g * granule) : nullptr;
     const uint4* __restrict__ px =
         reinterpret_cast<const uint4*>(src + g * granule);
     uint4* image16 = reinterpret_cast<uint4*>(image);
+    uint4* x16 = image16 + (kDict ? n16 : 0);
     uint4* table16 = reinterpret_cast<uint4*>(table);
 #pragma unroll 4
     for (uint32_t i = lane; i < n16; i += 64) {
-      image16[i] = pd[i];
-      image16[n16 + i] = px[i];
+      if (kDict) image16[i] = pd[i];
+      x16[i] = px[i];
     }
     for (uint32_t i = lane; i < kLzTableBytes / 16; i += 64) {
       table16[i] = make_uint4(0, 0, 0, 0);
     }
     wave_sync();
-    const uint32_t* image32 = reinterpret_cast<const uint32_t*>(image);
-    for (uint32_t q = lane; q < granule; q += 64) {  // q + 8 <= 2G
-      const uint32_t v = lds_u32(image32, q);
-      atomicMax(&table[(v * kLzHashMul) >> (32 - kLzHashBits)], q + 1);
+    if (kDict) {
+      const uint32_t* image32 = reinterpret_cast<const uint32_t*>(image);
+      for (uint32_t q = lane; q < granule; q += 64) {  // q + 8 <= 2G
+        const uint32_t v = lds_u32(image32, q);
+        atomicMax(&table[(v * kLzHashMul) >> (32 - kLzHashBits)], q + 1);
+      }
+      wave_sync();
     }
-    wave_sync();
-    const uint32_t size = lz_parse<true>(image, out, table, granule, lane);
+    const uint32_t size = lz_parse<kDict>(image, out, table, granule, lane);
     // size < granule and granule % 16 == 0: the pad stays inside `out`.
     if (size != granule && lane < ((16 - (size & 15)) & 15)) {
       out[size + lane] = 0;
     }
     wave_sync();
-    const uint4* from = size == granule ? image16 + n16
-                                        : reinterpret_cast<const uint4*>(out);
+    const uint4* from =
+        size == granule ? x16 : reinterpret_cast<const uint4*>(out);
     uint4* __restrict__ ps = reinterpret_cast<uint4*>(
         scratch + static_cast<uint64_t>(slot) * granule);
     for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) ps[i] = from[i];
@@ -400,55 +367,18 @@ __device__ __forceinline__ bool lz_decode(const uint8_t* piece, uint32_t size,
 // offsets[slot]) becomes the marked granule of that rank; unmarked
 // granules are never written. bad[slot] is written for every piece of
 // the window: 0, or 1 when the piece could not be decoded, in which case
-// its granule is left alone. kStrict: lz_decode's; `dense` is then the
-// device buffer k_xts_var decrypted the window into.
-template <bool kStrict = false>
+// its granule is left alone. Per-wave LDS: the piece (G) and the image
+// (G). kStrict: lz_decode's; `dense` is then the device buffer k_xts_var
+// decrypted the window into.
+//
+// kDict is HSLZD1: the dictionary of a piece is what its granule of `dst`
+// holds now, and the image is 2G. The wave reads the granule into
+// image[0, G), decodes into image[G, 2G) and only then writes the
+// granule, so it reads its target before it overwrites it; it touches no
+// other granule, so waves need no order. A raw piece is copied straight
+// and reads nothing of `dst`.
+template <bool kDict, bool kStrict>
 __global__ __launch_bounds__(kWavesPerWg * 64) void k_lz_decompress_marked(
-    uint8_t* __restrict__ dst, const uint8_t* __restrict__ dense,
-    const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
-    uint8_t* __restrict__ bad, const unsigned long long* __restrict__ bitmap,
-    const uint32_t* __restrict__ rank_before_word, MarkedWindow win,
-    uint32_t granule) {
-  extern __shared__ uint4 lz_lds[];
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n16 = granule >> 4;
-  uint4* piece16 = lz_lds + (threadIdx.x >> 6) * (2 * n16);
-  uint4* image16 = piece16 + n16;
-  wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
-                                                      uint32_t slot) {
-    const uint32_t size = uniform(sizes[slot]);
-    const uint4* __restrict__ pp =
-        reinterpret_cast<const uint4*>(dense + offsets[slot]);
-    uint4* __restrict__ pd = reinterpret_cast<uint4*>(dst + g * granule);
-    bool ok = size != 0 && size <= granule;
-    if (size == granule) {  // raw
-#pragma unroll 4
-      for (uint32_t i = lane; i < n16; i += 64) pd[i] = pp[i];
-    } else if (ok) {
-      for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) piece16[i] = pp[i];
-      wave_sync();
-      ok = lz_decode<kStrict>(reinterpret_cast<const uint8_t*>(piece16), size,
-                              reinterpret_cast<uint8_t*>(image16), 0, granule,
-                              lane);
-      wave_sync();
-      if (ok) {
-#pragma unroll 4
-        for (uint32_t i = lane; i < n16; i += 64) pd[i] = image16[i];
-      }
-      wave_sync();  // the next piece overwrites this LDS
-    }
-    if (lane == 0) bad[slot] = ok ? 0 : 1;
-  });
-}
-
-// k_lz_decompress_marked with HSLZD1: the dictionary of a piece is what
-// its granule of `dst` holds now. Per-wave LDS: the piece (G) and the
-// image (2G). The wave reads the granule into image[0, G), decodes into
-// image[G, 2G) and only then writes the granule, so it reads its target
-// before it overwrites it; it touches no other granule, so waves need no
-// order. A raw piece is copied straight and reads nothing of `dst`.
-template <bool kStrict = false>
-__global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_decompress_marked(
     uint8_t* dst, const uint8_t* __restrict__ dense,
     const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
     uint8_t* __restrict__ bad, const unsigned long long* __restrict__ bitmap,
@@ -457,8 +387,9 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_decompress_marked(
   extern __shared__ uint4 lz_lds[];
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t n16 = granule >> 4;
-  uint4* piece16 = lz_lds + (threadIdx.x >> 6) * (3 * n16);
+  uint4* piece16 = lz_lds + (threadIdx.x >> 6) * ((kDict ? 3 : 2) * n16);
   uint4* image16 = piece16 + n16;
+  uint4* x16 = image16 + (kDict ? n16 : 0);  // where the granule is decoded
   wave_window_walk(bitmap, rank_before_word, win, [&](uint64_t g,
                                                       uint32_t slot) {
     const uint32_t size = uniform(sizes[slot]);
@@ -471,16 +402,19 @@ __global__ __launch_bounds__(kWavesPerWg * 64) void k_lzd_decompress_marked(
       for (uint32_t i = lane; i < n16; i += 64) pd[i] = pp[i];
     } else if (ok) {
       for (uint32_t i = lane; i < (size + 15) >> 4; i += 64) piece16[i] = pp[i];
+      if (kDict) {
 #pragma unroll 4
-      for (uint32_t i = lane; i < n16; i += 64) image16[i] = pd[i];
+        for (uint32_t i = lane; i < n16; i += 64) image16[i] = pd[i];
+      }
       wave_sync();
+      const uint32_t start = kDict ? granule : 0;
       ok = lz_decode<kStrict>(reinterpret_cast<const uint8_t*>(piece16), size,
-                              reinterpret_cast<uint8_t*>(image16), granule,
-                              2 * granule, lane);
+                              reinterpret_cast<uint8_t*>(image16), start,
+                              start + granule, lane);
       wave_sync();
       if (ok) {
 #pragma unroll 4
-        for (uint32_t i = lane; i < n16; i += 64) pd[i] = image16[n16 + i];
+        for (uint32_t i = lane; i < n16; i += 64) pd[i] = x16[i];
       }
       wave_sync();  // the next piece overwrites this LDS
     }
@@ -635,48 +569,42 @@ int check_window_sizes(const std::vector<uint64_t>& bitmap,
   return kIoOk;
 }
 
-// What both GPU window loops run on: HalvesStream's `done` events end a
-// half's last kernel, `packed` ends k_lz_compress_marked alone. With
-// `dictionary` the HSLZD1 kernels run: compress reads the dictionaries
-// at `dict`, decompress takes them from the target itself.
-struct LzStream : HalvesStream {
+// What both GPU window loops run on: the window stream, its staging the
+// dense pieces, with the per-piece arrays. `done` events end a half's last
+// kernel, `packed` ends k_lz_compress_marked alone. With `dictionary` the
+// HSLZD1 kernels run: compress reads the dictionaries at `dict`,
+// decompress takes them from the target itself.
+struct LzStream : WindowStream {
   hipEvent_t packed[2] = {nullptr, nullptr};
-  uint32_t granule;
   uint64_t chunk;  // granules per half
   uint8_t* scratch = nullptr;
-  uint8_t* dense;
   uint32_t* sizes;
   uint64_t* offsets;
   uint8_t* bad;
-  const unsigned long long* dev_words;
-  const uint32_t* dev_ranks;
-  uint8_t* base;  // the bdev's range in device memory
   bool dictionary;
   const uint8_t* dict;  // the base volume's range in device memory
   // A keyed call: k_xts_var encrypts the pieces on their way from scratch
-  // to `dense` and decrypts them on their way back into scratch, where
-  // the strict decode kernels read them. The copy of the schedules here
-  // is cleared with the object.
+  // to the dense halves and decrypts them on their way back into scratch,
+  // where the strict decode kernels read them. The copy of the schedules
+  // here is cleared with the object.
   bool keyed;
   uint64_t first_unit;
   XtsKernelKeys keys;
 
   LzStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
            const MarkedPlan& plan, bool compress, const LzKey& key,
-           bool with_dictionary = false, const uint8_t* dict_range = nullptr)
-      : HalvesStream(device), granule(granule_bytes),
+           bool with_dictionary, const uint8_t* dict_range)
+      : WindowStream(device, bdev, offset, granule_bytes, plan,
+                     compress_ctx().dense),
         chunk(plan.chunk_granules),
-        dense(compress_ctx().dense.reserve(2 * chunk * granule)),
         sizes(compress_ctx().sizes.reserve(2 * chunk)),
         offsets(compress_ctx().offsets.reserve(2 * chunk)),
         bad(compress_ctx().bad.reserve(2 * chunk)),
-        dev_words(device_view(plan.words)), dev_ranks(device_view(plan.ranks)),
-        base(static_cast<uint8_t*>(bdev->device_base()) + offset),
         dictionary(with_dictionary), dict(dict_range),
         keyed(static_cast<bool>(key)), first_unit(key.first_unit) {
     if (keyed) xts_load_kernel_keys(*key.schedules, compress, &keys);
     if (compress || keyed) {
-      scratch = compress_ctx().scratch.reserve(device, 2 * chunk * granule);
+      scratch = compress_ctx().scratch.reserve(device, 2 * half_bytes);
     }
     if (compress) {
       for (hipEvent_t& e : packed) {
@@ -692,28 +620,23 @@ struct LzStream : HalvesStream {
     explicit_bzero(&keys, sizeof(keys));
   }
 
+  // Launch geometry: the waves that fit the LDS, each with `per_wave`
+  // bytes of it. HSLZ1 takes 4, 2 or 1, HSLZD1 any of 1 .. 4.
+  uint32_t waves(uint32_t per_wave) const {
+    return dictionary ? lzd_waves(per_wave) : lz_waves(per_wave);
+  }
+
   void compress(const MarkedWindow& win, int half) {
-    if (dictionary) {
-      const uint32_t per_wave = 3 * granule + kLzTableBytes;
-      const uint32_t waves = lzd_waves(per_wave);
-      hipLaunchKernelGGL(k_lzd_compress_marked,
-                         dim3(wave_window_grid(win, waves)), dim3(waves * 64),
-                         waves * per_wave, stream, base, dict,
-                         scratch + half * chunk * granule,
-                         device_view(sizes + half * chunk), dev_words,
-                         dev_ranks, win, granule);
-    } else {
-      const uint32_t per_wave = 2 * granule + kLzTableBytes;
-      const uint32_t waves = lz_waves(per_wave);
-      hipLaunchKernelGGL(k_lz_compress_marked,
-                         dim3(wave_window_grid(win, waves)), dim3(waves * 64),
-                         waves * per_wave, stream, base,
-                         scratch + half * chunk * granule,
-                         device_view(sizes + half * chunk), dev_words,
-                         dev_ranks, win, granule);
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(packed[half], stream));
+    const uint32_t per_wave = (dictionary ? 3 : 2) * granule + kLzTableBytes;
+    const uint32_t n = waves(per_wave);
+    hipLaunchKernelGGL(dictionary ? k_lz_compress_marked<true>
+                                  : k_lz_compress_marked<false>,
+                       dim3(wave_window_grid(win, n)), dim3(n * 64),
+                       n * per_wave, stream, base, dict,
+                       scratch + half * half_bytes,
+                       device_view(sizes + half * chunk), dev_words, dev_ranks,
+                       win, granule);
+    record(packed[half]);
   }
 
   // After packed[half]: the sizes are in, the pieces follow.
@@ -721,33 +644,32 @@ struct LzStream : HalvesStream {
     piece_offsets(sizes + half * chunk, win.count, keyed ? 16 : 1,
                   offsets + half * chunk);
     if (keyed) {
-      xts_var_launch(true, stream, scratch + half * chunk * granule,
-                     device_view(dense + half * chunk * granule),
+      xts_var_launch(true, stream, scratch + half * half_bytes,
+                     dev_staging + half * half_bytes,
                      device_view(sizes + half * chunk),
                      device_view(offsets + half * chunk), dev_words, dev_ranks,
                      win, granule, first_unit, keys);
-      HIP_CHECK(hipEventRecord(done[half], stream));
-      return;
+    } else {
+      const uint32_t grid = std::min<uint32_t>(
+          (win.count + kWavesPerWg - 1) / kWavesPerWg, 2048);
+      hipLaunchKernelGGL(k_gather_var, dim3(grid), dim3(kWavesPerWg * 64), 0,
+                         stream, scratch + half * half_bytes,
+                         dev_staging + half * half_bytes,
+                         device_view(sizes + half * chunk),
+                         device_view(offsets + half * chunk), win.count,
+                         granule);
     }
-    const uint32_t grid = std::min<uint32_t>(
-        (win.count + kWavesPerWg - 1) / kWavesPerWg, 2048);
-    hipLaunchKernelGGL(k_gather_var, dim3(grid), dim3(kWavesPerWg * 64), 0,
-                       stream, scratch + half * chunk * granule,
-                       device_view(dense + half * chunk * granule),
-                       device_view(sizes + half * chunk),
-                       device_view(offsets + half * chunk), win.count, granule);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(done[half], stream));
+    record(done[half]);
   }
 
   // Keyed: the window's sizes were checked (check_window_sizes), so the
   // pieces at their offsets stay inside a half of scratch.
   void decompress(const MarkedWindow& win, int half) {
     const uint32_t per_wave = (dictionary ? 3 : 2) * granule;
-    const uint32_t waves = dictionary ? lzd_waves(per_wave) : lz_waves(per_wave);
-    const uint8_t* pieces = device_view(dense + half * chunk * granule);
+    const uint32_t n = waves(per_wave);
+    const uint8_t* pieces = dev_staging + half * half_bytes;
     if (keyed) {
-      uint8_t* plain = scratch + half * chunk * granule;
+      uint8_t* plain = scratch + half * half_bytes;
       xts_var_launch(false, stream, pieces, plain,
                      device_view(sizes + half * chunk),
                      device_view(offsets + half * chunk), dev_words, dev_ranks,
@@ -755,47 +677,43 @@ struct LzStream : HalvesStream {
       pieces = plain;
     }
     hipLaunchKernelGGL(dictionary
-                           ? (keyed ? k_lzd_decompress_marked<true>
-                                    : k_lzd_decompress_marked<false>)
-                           : (keyed ? k_lz_decompress_marked<true>
-                                    : k_lz_decompress_marked<false>),
-                       dim3(wave_window_grid(win, waves)),
-                       dim3(waves * 64), waves * per_wave, stream, base,
-                       pieces, device_view(sizes + half * chunk),
+                           ? (keyed ? k_lz_decompress_marked<true, true>
+                                    : k_lz_decompress_marked<true, false>)
+                           : (keyed ? k_lz_decompress_marked<false, true>
+                                    : k_lz_decompress_marked<false, false>),
+                       dim3(wave_window_grid(win, n)), dim3(n * 64),
+                       n * per_wave, stream, base, pieces,
+                       device_view(sizes + half * chunk),
                        device_view(offsets + half * chunk),
                        device_view(bad + half * chunk), dev_words, dev_ranks,
                        win, granule);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(done[half], stream));
+    record(done[half]);
   }
 };
 
-// Window k+1 is compressed while the sink has window k: one stream, so
-// the order on the device is compress k, gather k, compress k+1, ...
+// The shared pack loop with a window in two steps: once its sizes are in
+// (packed), its pieces are gathered behind it. Window k+1 is compressed
+// while the sink has window k: one stream, so the order on the device is
+// compress k, gather k, compress k+1, ...
 int compress_gpu(LzStream& ls, const MarkedPlan& plan, const CompressSink& sink,
                  uint64_t* packed) {
-  MarkedWindow cur = next_marked_window(plan, 0, 0);
-  ls.compress(cur, 0);
-  for (int half = 0;; half ^= 1) {
-    const uint64_t next_rank = cur.first_rank + static_cast<uint64_t>(cur.count);
-    wait_marked_event(ls.packed[half]);
-    ls.gather(cur, half);
-    MarkedWindow next{};
-    if (next_rank < plan.marked) {
-      next = next_marked_window(plan, cur.g_end, next_rank);
-      ls.compress(next, half ^ 1);
-    }
-    wait_marked_event(ls.done[half]);
-    const int status =
-        sink(ls.dense + half * ls.chunk * ls.granule,
-             ls.sizes + half * ls.chunk, cur.first_rank, cur.count);
-    if (status != 0) return status;
-    *packed = next_rank;
-    if (next_rank >= plan.marked) return kIoOk;
-    cur = next;
-  }
+  return pack_windows(
+      ls, plan,
+      [&](const MarkedWindow& win, int half) { ls.compress(win, half); },
+      [&](const MarkedWindow& win, int half) {
+        wait_marked_event(ls.packed[half]);
+        ls.gather(win, half);
+      },
+      [&](const MarkedWindow& win, int half) {
+        return sink(ls.half_of(half), ls.sizes + half * ls.chunk,
+                    win.first_rank, win.count);
+      },
+      packed);
 }
 
+// The shared unpack loop; a window is checked on the host before its
+// launch, and the flags of a half's last kernel are read before the half
+// is used again and, for the kernels still out at the end, after the loop.
 int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
                    const std::vector<uint64_t>& bitmap,
                    const DecompressSource& source, uint64_t* unpacked,
@@ -817,38 +735,32 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
     return true;
   };
   const int gave_up_status = ls.keyed ? kIoInvalid : kIoFailed;
-  uint64_t g_begin = 0;
-  uint64_t launched = 0;
-  int status = kIoOk;
-  for (int half = 0; launched < plan.marked && status == kIoOk; half ^= 1) {
-    const MarkedWindow win = next_marked_window(plan, g_begin, launched);
-    // The kernel two windows back read this half: let it finish first.
-    if (in_half[half] != 0) {
-      wait_marked_event(ls.done[half]);
-      if (gave_up(half)) status = gave_up_status;
-      in_half[half] = 0;
-      if (status != kIoOk) break;
-    }
-    uint8_t* data = ls.dense + half * ls.chunk * ls.granule;
-    uint32_t* sizes = ls.sizes + half * ls.chunk;
-    status = source(data, sizes, win.first_rank, win.count);
-    if (status == 0) {
-      status = ls.keyed
+  int status = unpack_windows(
+      ls, plan,
+      [&](int half) -> int {
+        const bool bad = gave_up(half);
+        in_half[half] = 0;
+        return bad ? gave_up_status : kIoOk;
+      },
+      [&](const MarkedWindow& win, int half) -> int {
+        uint8_t* data = ls.half_of(half);
+        uint32_t* sizes = ls.sizes + half * ls.chunk;
+        const int got = source(data, sizes, win.first_rank, win.count);
+        if (got != 0) return got;
+        return ls.keyed
                    ? check_window_sizes(bitmap, sizes, win.first_rank,
                                         win.count, ls.granule,
                                         ls.offsets + half * ls.chunk, error)
                    : check_window(bitmap, data, sizes, win.first_rank,
                                   win.count, ls.granule, ls.dictionary, 1,
                                   ls.offsets + half * ls.chunk, error);
-    }
-    if (status != kIoOk) break;
-    ls.decompress(win, half);
-    in_half[half] = win.count;
-    rank_of[half] = win.first_rank;
-    launched += win.count;
-    g_begin = win.g_end;
-  }
-  HIP_CHECK(hipStreamSynchronize(ls.stream));
+      },
+      [&](const MarkedWindow& win, int half) {
+        ls.decompress(win, half);
+        in_half[half] = win.count;
+        rank_of[half] = win.first_rank;
+      },
+      unpacked);
   // The older window first, so that the lowest bad granule is named.
   const int older = rank_of[0] <= rank_of[1] ? 0 : 1;
   if (gave_up(older) || gave_up(older ^ 1)) {
@@ -858,36 +770,8 @@ int decompress_gpu(LzStream& ls, const MarkedPlan& plan,
                              : "k_lz_decompress_marked gave up on a piece";
     }
   }
-  *unpacked = launched;
   return status;
 }
-
-// The marked granules of a range in ascending order, for the generic
-// HSLZD1 paths, whose chunks arrive in that order and need the index of
-// every granule to find its dictionary.
-struct MarkCursor {
-  const std::vector<uint64_t>& bitmap;
-  uint64_t n_granules;
-  uint64_t w = 0;
-  uint64_t word = 0;
-  bool loaded = false;
-
-  // The caller takes no more granules than the range has marks.
-  uint64_t next() {
-    for (;; ++w, loaded = false) {
-      if (!loaded) {
-        word = bitmap[w];
-        const uint64_t left = n_granules - w * 64;
-        if (left < 64) word &= (1ull << left) - 1;
-        loaded = true;
-      }
-      if (word != 0) break;
-    }
-    const uint64_t g = w * 64 + static_cast<uint64_t>(__builtin_ctzll(word));
-    word &= word - 1;
-    return g;
-  }
-};
 
 // Generic paths: bdev_pack_marked_sync / bdev_unpack_marked_sync cut the
 // chunks, the host codec does the rest. With `base` (HSLZD1) the
@@ -990,39 +874,31 @@ int decompress_generic(Bdev* dst, uint64_t offset, uint64_t length,
       unpacked);
 }
 
-// Validation and plan of both calls; chunking as marked_stream_sync.
-// kIoOk with plan->marked == 0 means nothing to do. A key (any of the
-// two arguments set) must pass xts_key_ok and leave every unit number
-// below 2^64-1.
+// What is the codec's to check before the shared plan
+// (plan_marked_windows): the granule, and a key (any of the two fields
+// set), which must pass xts_key_ok and leave every unit number below
+// 2^64-1.
 int lz_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
-            const std::vector<uint64_t>& bitmap, uint64_t staging_bytes,
-            bool have_callback, const uint8_t* key, size_t key_len,
-            uint64_t first_unit, MarkedPlan* plan, std::string* error) {
+            const std::vector<uint64_t>& bitmap, const LzOptions& options,
+            bool have_callback, MarkedPlan* plan, std::string* error) {
+  const XtsKey& key = options.key;
   if (!lz_granule_ok(granule)) {
     if (error != nullptr) {
       *error = "compression needs 512 <= granule <= 16384, a multiple of 16";
     }
     return kIoInvalid;
   }
-  if ((key != nullptr || key_len != 0) && !xts_key_ok(key, key_len)) {
+  if ((key.key != nullptr || key.len != 0) && !xts_key_ok(key.key, key.len)) {
     if (error != nullptr) {
       *error = "the key must be 64 bytes whose halves differ";
     }
     return kIoInvalid;
   }
-  if (!granule_ranges_ok(bdev, offset, bdev, offset, length, granule,
-                         &bitmap) ||
-      (staging_bytes != 0 && staging_bytes < granule) ||
-      (key != nullptr && length / granule > kXtsKcvUnit - first_unit)) {
+  if (key.key != nullptr && length / granule > kXtsKcvUnit - key.first_unit) {
     return kIoInvalid;
   }
-  *plan = build_marked_plan(length / granule, bitmap, true);
-  if (plan->marked != 0 && !have_callback) return kIoInvalid;
-  const uint64_t half =
-      staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
-  plan->chunk_granules =
-      std::min(std::max<uint64_t>(1, half / granule), plan->marked);
-  return kIoOk;
+  return plan_marked_windows(bdev, offset, length, granule, bitmap,
+                             options.staging_bytes, have_callback, plan);
 }
 
 // The schedules of a call's key, if it has one, for as long as the call
@@ -1030,10 +906,10 @@ int lz_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
 struct CallKey {
   std::unique_ptr<XtsSchedules> schedules;
   LzKey key;
-  CallKey(const uint8_t* raw, uint64_t first_unit) {
-    if (raw == nullptr) return;
-    schedules.reset(new XtsSchedules(raw));
-    key = {schedules.get(), first_unit};
+  explicit CallKey(const XtsKey& raw) {
+    if (raw.key == nullptr) return;
+    schedules.reset(new XtsSchedules(raw.key));
+    key = {schedules.get(), raw.first_unit};
   }
 };
 
@@ -1042,140 +918,73 @@ struct CallKey {
 int bdev_compress_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               uint32_t granule,
                               const std::vector<uint64_t>& bitmap,
-                              uint64_t staging_bytes, const CompressSink& sink,
-                              uint64_t* packed_out, std::string* error,
-                              const uint8_t* key, size_t key_len,
-                              uint64_t first_unit) {
-  uint64_t unused = 0;
-  uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
-  *packed = 0;
-  try {
+                              const LzOptions& options,
+                              const CompressSink& sink, uint64_t* packed_out,
+                              std::string* error) {
+  Bdev* base = options.base;
+  return marked_call(packed_out, [&](uint64_t* packed) -> int {
+    if (base != nullptr) {
+      if (!granule_ranges_ok(src, src_offset, base, options.base_offset,
+                             length, granule, &bitmap)) {
+        return kIoInvalid;
+      }
+      // Overlap is only possible within one backing store (validated
+      // ranges: the difference below cannot wrap).
+      const void* s_base = src->device_base();
+      const bool same_store =
+          src == base || (s_base != nullptr && s_base == base->device_base() &&
+                          src->gpu_device() == base->gpu_device());
+      if (same_store && std::max(src_offset, options.base_offset) -
+                                std::min(src_offset, options.base_offset) <
+                            length) {
+        if (error != nullptr) *error = "the volume and its base overlap";
+        return kIoInvalid;
+      }
+    }
     MarkedPlan plan;
     const int status = lz_plan(src, src_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(sink), key,
-                               key_len, first_unit, &plan, error);
+                               options, static_cast<bool>(sink), &plan, error);
     if (status != kIoOk || plan.marked == 0) return status;
-    const CallKey call(key, first_unit);
-    const int device = granule_kernel_device(src, src);
+    const CallKey call(options.key);
+    const int device = granule_kernel_device(src, base != nullptr ? base : src);
     if (device < 0) {
-      return compress_generic(src, src_offset, nullptr, 0, length, granule,
-                              bitmap, staging_bytes, sink, call.key, packed);
+      return compress_generic(src, src_offset, base, options.base_offset,
+                              length, granule, bitmap, options.staging_bytes,
+                              sink, call.key, packed);
     }
-    LzStream ls(device, src, src_offset, granule, plan, true, call.key);
+    LzStream ls(device, src, src_offset, granule, plan, true, call.key,
+                base != nullptr,
+                base != nullptr
+                    ? static_cast<const uint8_t*>(base->device_base()) +
+                          options.base_offset
+                    : nullptr);
     return compress_gpu(ls, plan, sink, packed);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
+  });
 }
 
 int bdev_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 uint64_t length, uint32_t granule,
                                 const std::vector<uint64_t>& bitmap,
-                                uint64_t staging_bytes,
+                                const LzOptions& options,
                                 const DecompressSource& source,
-                                uint64_t* unpacked_out, std::string* error,
-                                const uint8_t* key, size_t key_len,
-                                uint64_t first_unit) {
-  uint64_t unused = 0;
-  uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
-  *unpacked = 0;
-  try {
+                                uint64_t* unpacked_out, std::string* error) {
+  return marked_call(unpacked_out, [&](uint64_t* unpacked) -> int {
     MarkedPlan plan;
-    const int status = lz_plan(dst, dst_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(source), key,
-                               key_len, first_unit, &plan, error);
+    const int status =
+        lz_plan(dst, dst_offset, length, granule, bitmap, options,
+                static_cast<bool>(source), &plan, error);
     if (status != kIoOk || plan.marked == 0) return status;
-    const CallKey call(key, first_unit);
+    const CallKey call(options.key);
     const int device = granule_kernel_device(dst, dst);
     if (device < 0) {
       return decompress_generic(dst, dst_offset, length, granule, bitmap,
-                                staging_bytes, source, false, call.key,
-                                unpacked, error);
+                                options.staging_bytes, source,
+                                options.dictionary, call.key, unpacked, error);
     }
-    LzStream ls(device, dst, dst_offset, granule, plan, false, call.key);
+    LzStream ls(device, dst, dst_offset, granule, plan, false, call.key,
+                options.dictionary, nullptr);
     return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
-}
-
-int bdev_dict_compress_marked_sync(Bdev* src, uint64_t src_offset, Bdev* base,
-                                   uint64_t base_offset, uint64_t length,
-                                   uint32_t granule,
-                                   const std::vector<uint64_t>& bitmap,
-                                   uint64_t staging_bytes,
-                                   const CompressSink& sink,
-                                   uint64_t* packed_out, std::string* error,
-                                   const uint8_t* key, size_t key_len,
-                                   uint64_t first_unit) {
-  uint64_t unused = 0;
-  uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
-  *packed = 0;
-  try {
-    if (!granule_ranges_ok(src, src_offset, base, base_offset, length, granule,
-                           &bitmap)) {
-      return kIoInvalid;
-    }
-    // Overlap is only possible within one backing store (validated
-    // ranges: the difference below cannot wrap).
-    const void* s_base = src->device_base();
-    const bool same_store =
-        src == base || (s_base != nullptr && s_base == base->device_base() &&
-                        src->gpu_device() == base->gpu_device());
-    if (same_store && std::max(src_offset, base_offset) -
-                              std::min(src_offset, base_offset) < length) {
-      if (error != nullptr) *error = "the volume and its base overlap";
-      return kIoInvalid;
-    }
-    MarkedPlan plan;
-    const int status = lz_plan(src, src_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(sink), key,
-                               key_len, first_unit, &plan, error);
-    if (status != kIoOk || plan.marked == 0) return status;
-    const CallKey call(key, first_unit);
-    const int device = granule_kernel_device(src, base);
-    if (device < 0) {
-      return compress_generic(src, src_offset, base, base_offset, length,
-                              granule, bitmap, staging_bytes, sink, call.key,
-                              packed);
-    }
-    LzStream ls(device, src, src_offset, granule, plan, true, call.key, true,
-                static_cast<const uint8_t*>(base->device_base()) + base_offset);
-    return compress_gpu(ls, plan, sink, packed);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
-}
-
-int bdev_dict_decompress_marked_sync(Bdev* dst, uint64_t dst_offset,
-                                     uint64_t length, uint32_t granule,
-                                     const std::vector<uint64_t>& bitmap,
-                                     uint64_t staging_bytes,
-                                     const DecompressSource& source,
-                                     uint64_t* unpacked_out,
-                                     std::string* error, const uint8_t* key,
-                                     size_t key_len, uint64_t first_unit) {
-  uint64_t unused = 0;
-  uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
-  *unpacked = 0;
-  try {
-    MarkedPlan plan;
-    const int status = lz_plan(dst, dst_offset, length, granule, bitmap,
-                               staging_bytes, static_cast<bool>(source), key,
-                               key_len, first_unit, &plan, error);
-    if (status != kIoOk || plan.marked == 0) return status;
-    const CallKey call(key, first_unit);
-    const int device = granule_kernel_device(dst, dst);
-    if (device < 0) {
-      return decompress_generic(dst, dst_offset, length, granule, bitmap,
-                                staging_bytes, source, true, call.key, unpacked,
-                                error);
-    }
-    LzStream ls(device, dst, dst_offset, granule, plan, false, call.key, true);
-    return decompress_gpu(ls, plan, bitmap, source, unpacked, error);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
+  });
 }
 
 }  // namespace hipstore

@@ -56,6 +56,7 @@
 
 #include <algorithm>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include "crypt_internal.h"
@@ -503,118 +504,67 @@ void load_words(const uint8_t* schedule, uint32_t* words) {
   }
 }
 
-// What both GPU window loops run on: MarkedStream of bulk_ops.hip with
-// the keys. The copy of the schedules here is cleared with the object;
-// what a launch copied into the runtime's argument memory is not ours.
-struct XtsStream : HalvesStream {
-  uint32_t granule;
-  uint64_t half_bytes;
+// What both GPU window loops run on: the window stream with the keys.
+// The copy of the schedules here is cleared with the object; what a
+// launch copied into the runtime's argument memory is not ours.
+struct XtsStream : WindowStream {
   uint64_t first_unit;
-  uint8_t* staging;
-  uint8_t* dev_staging;
-  const unsigned long long* dev_words;
-  const uint32_t* dev_ranks;
-  uint8_t* base;  // the bdev's range in device memory
   XtsKernelKeys keys;
 
   XtsStream(int device, Bdev* bdev, uint64_t offset, uint32_t granule_bytes,
             const MarkedPlan& plan, const XtsSchedules& schedules,
             bool encrypt, uint64_t first)
-      : HalvesStream(device), granule(granule_bytes),
-        half_bytes(plan.chunk_granules * granule_bytes), first_unit(first),
-        staging(xts_staging().reserve(2 * half_bytes)),
-        dev_staging(device_view(staging)), dev_words(device_view(plan.words)),
-        dev_ranks(device_view(plan.ranks)),
-        base(static_cast<uint8_t*>(bdev->device_base()) + offset) {
+      : WindowStream(device, bdev, offset, granule_bytes, plan, xts_staging()),
+        first_unit(first) {
     xts_load_kernel_keys(schedules, encrypt, &keys);
   }
   ~XtsStream() { explicit_bzero(&keys, sizeof(keys)); }
 
   template <typename Kernel>
   void launch(Kernel kernel, const MarkedWindow& win, int half) {
-    hipLaunchKernelGGL(kernel, dim3(wave_window_grid(win, kXtsThreads / 64)),
-                       dim3(kXtsThreads), 0, stream, base,
-                       dev_staging + half * half_bytes, dev_words, dev_ranks,
-                       win, granule, first_unit, keys);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(done[half], stream));
+    WindowStream::launch(kernel, wave_window_grid(win, kXtsThreads / 64),
+                         kXtsThreads, win, half, first_unit, keys);
   }
 };
 
-// Pack launches one window ahead, then waits for the current one.
-int xts_pack_gpu(XtsStream& xs, const MarkedPlan& plan, const PackSink& sink,
-                 uint64_t* packed) {
-  MarkedWindow cur = next_marked_window(plan, 0, 0);
-  xs.launch(k_xts_pack_marked, cur, 0);
-  for (int half = 0;; half ^= 1) {
-    const uint64_t next_rank = cur.first_rank + static_cast<uint64_t>(cur.count);
-    MarkedWindow next{};
-    if (next_rank < plan.marked) {
-      next = next_marked_window(plan, cur.g_end, next_rank);
-      xs.launch(k_xts_pack_marked, next, half ^ 1);
-    }
-    wait_marked_event(xs.done[half]);
-    const int status =
-        sink(xs.staging + half * xs.half_bytes, cur.first_rank, cur.count);
-    if (status != 0) return status;
-    *packed = next_rank;
-    if (next_rank >= plan.marked) return kIoOk;
-    cur = next;
-  }
+// k_xts_pack_marked per window on the shared pack loop.
+int xts_gpu(XtsStream& xs, const MarkedPlan& plan, const PackSink& sink,
+            uint64_t* packed) {
+  return pack_windows(
+      xs, plan,
+      [&](const MarkedWindow& win, int half) {
+        xs.launch(k_xts_pack_marked, win, half);
+      },
+      [](const MarkedWindow&, int) {},
+      [&](const MarkedWindow& win, int half) {
+        return sink(xs.half_of(half), win.first_rank, win.count);
+      },
+      packed);
 }
 
-int xts_unpack_gpu(XtsStream& xs, const MarkedPlan& plan,
-                   const UnpackSource& source, uint64_t* unpacked) {
-  bool used[2] = {false, false};
-  uint64_t g_begin = 0;
-  uint64_t launched = 0;
-  for (int half = 0; launched < plan.marked; half ^= 1) {
-    const MarkedWindow win = next_marked_window(plan, g_begin, launched);
-    // The kernel two windows back read this half: let it finish first.
-    if (used[half]) wait_marked_event(xs.done[half]);
-    const int status =
-        source(xs.staging + half * xs.half_bytes, win.first_rank, win.count);
-    if (status != 0) {
-      HIP_CHECK(hipStreamSynchronize(xs.stream));
-      *unpacked = launched;
-      return status;
-    }
-    xs.launch(k_xts_unpack_marked, win, half);
-    used[half] = true;
-    launched += win.count;
-    g_begin = win.g_end;
-  }
-  HIP_CHECK(hipStreamSynchronize(xs.stream));
-  *unpacked = launched;
-  return kIoOk;
+// k_xts_unpack_marked per window on the shared unpack loop.
+int xts_gpu(XtsStream& xs, const MarkedPlan& plan, const UnpackSource& source,
+            uint64_t* unpacked) {
+  return unpack_windows(
+      xs, plan, [](int) { return 0; },
+      [&](const MarkedWindow& win, int half) {
+        return source(xs.half_of(half), win.first_rank, win.count);
+      },
+      [&](const MarkedWindow& win, int half) {
+        xs.launch(k_xts_unpack_marked, win, half);
+      },
+      unpacked);
 }
 
 // Generic paths: bdev_pack_marked_sync / bdev_unpack_marked_sync cut the
 // chunks, the host codec does the rest. Chunks arrive in rank order, so
-// one cursor over the bitmap gives every granule its unit number.
-struct MarkCursor {
-  const std::vector<uint64_t>& bitmap;
-  uint64_t w = 0;
-  uint64_t word;
-
-  explicit MarkCursor(const std::vector<uint64_t>& b)
-      : bitmap(b), word(b.empty() ? 0 : b[0]) {}
-  // Index of the next marked granule; the caller knows there is one.
-  uint64_t next() {
-    while (word == 0) word = bitmap[++w];
-    const uint64_t g = w * 64 + static_cast<uint64_t>(__builtin_ctzll(word));
-    word &= word - 1;
-    return g;
-  }
-};
-
-int xts_pack_generic(Bdev* src, uint64_t offset, uint64_t length,
-                     uint32_t granule, const std::vector<uint64_t>& bitmap,
-                     const XtsSchedules& keys, uint64_t first_unit,
-                     uint64_t staging_bytes, const PackSink& sink,
-                     uint64_t* packed) {
+// one MarkCursor over the bitmap gives every granule its unit number.
+int xts_generic(Bdev* src, uint64_t offset, uint64_t length, uint32_t granule,
+                const std::vector<uint64_t>& bitmap, const XtsSchedules& keys,
+                uint64_t first_unit, uint64_t staging_bytes,
+                const PackSink& sink, uint64_t* packed) {
   std::vector<uint8_t> out;
-  MarkCursor marks(bitmap);
+  MarkCursor marks{bitmap, length / granule};
   return bdev_pack_marked_sync(
       src, offset, length, granule, bitmap, staging_bytes,
       [&](const uint8_t* data, uint64_t first_rank, uint64_t count) {
@@ -628,12 +578,11 @@ int xts_pack_generic(Bdev* src, uint64_t offset, uint64_t length,
       packed);
 }
 
-int xts_unpack_generic(Bdev* dst, uint64_t offset, uint64_t length,
-                       uint32_t granule, const std::vector<uint64_t>& bitmap,
-                       const XtsSchedules& keys, uint64_t first_unit,
-                       uint64_t staging_bytes, const UnpackSource& source,
-                       uint64_t* unpacked) {
-  MarkCursor marks(bitmap);
+int xts_generic(Bdev* dst, uint64_t offset, uint64_t length, uint32_t granule,
+                const std::vector<uint64_t>& bitmap, const XtsSchedules& keys,
+                uint64_t first_unit, uint64_t staging_bytes,
+                const UnpackSource& source, uint64_t* unpacked) {
+  MarkCursor marks{bitmap, length / granule};
   return bdev_unpack_marked_sync(
       dst, offset, length, granule, bitmap, staging_bytes,
       [&](uint8_t* data, uint64_t first_rank, uint64_t count) {
@@ -649,26 +598,34 @@ int xts_unpack_generic(Bdev* dst, uint64_t offset, uint64_t length,
       unpacked);
 }
 
-// Validation and plan of both calls; chunking as marked_stream_sync.
-// kIoOk with plan->marked == 0 means nothing to do.
-int xts_plan(Bdev* bdev, uint64_t offset, uint64_t length, uint32_t granule,
-             const std::vector<uint64_t>& bitmap, const uint8_t* key,
-             size_t key_len, uint64_t first_unit, uint64_t staging_bytes,
-             bool have_callback, MarkedPlan* plan) {
-  if (!xts_key_ok(key, key_len) || !xts_granule_ok(granule) ||
-      !granule_ranges_ok(bdev, offset, bdev, offset, length, granule,
-                         &bitmap) ||
-      (staging_bytes != 0 && staging_bytes < granule) ||
-      length / granule > kXtsKcvUnit - first_unit) {
-    return kIoInvalid;
-  }
-  *plan = build_marked_plan(length / granule, bitmap, true);
-  if (plan->marked != 0 && !have_callback) return kIoInvalid;
-  const uint64_t half =
-      staging_bytes == 0 ? kDefaultStagingHalf : staging_bytes / 2;
-  plan->chunk_granules =
-      std::min(std::max<uint64_t>(1, half / granule), plan->marked);
-  return kIoOk;
+// bdev_xts_pack_marked_sync (Chunk = PackSink) and
+// bdev_xts_unpack_marked_sync (Chunk = UnpackSource): what is the key's
+// to check, then the shared plan, then the GPU or the generic path.
+template <typename Chunk>
+int xts_marked_sync(Bdev* bdev, uint64_t offset, uint64_t length,
+                    uint32_t granule, const std::vector<uint64_t>& bitmap,
+                    const XtsKey& key, uint64_t staging_bytes,
+                    const Chunk& chunk, uint64_t* moved_out) {
+  return marked_call(moved_out, [&](uint64_t* moved) -> int {
+    if (!xts_key_ok(key.key, key.len) || !xts_granule_ok(granule) ||
+        length / granule > kXtsKcvUnit - key.first_unit) {
+      return kIoInvalid;
+    }
+    MarkedPlan plan;
+    const int status =
+        plan_marked_windows(bdev, offset, length, granule, bitmap,
+                            staging_bytes, static_cast<bool>(chunk), &plan);
+    if (status != kIoOk || plan.marked == 0) return status;
+    const XtsSchedules schedules(key.key);
+    const int device = granule_kernel_device(bdev, bdev);
+    if (device < 0) {
+      return xts_generic(bdev, offset, length, granule, bitmap, schedules,
+                         key.first_unit, staging_bytes, chunk, moved);
+    }
+    XtsStream xs(device, bdev, offset, granule, plan, schedules,
+                 std::is_same<Chunk, PackSink>::value, key.first_unit);
+    return xts_gpu(xs, plan, chunk, moved);
+  });
 }
 
 }  // namespace
@@ -695,62 +652,20 @@ void xts_var_launch(bool encrypt, hipStream_t stream, const uint8_t* from,
 int bdev_xts_pack_marked_sync(Bdev* src, uint64_t src_offset, uint64_t length,
                               uint32_t granule,
                               const std::vector<uint64_t>& bitmap,
-                              const uint8_t* key, size_t key_len,
-                              uint64_t first_unit, uint64_t staging_bytes,
-                              const PackSink& sink, uint64_t* packed_out) {
-  uint64_t unused = 0;
-  uint64_t* packed = packed_out != nullptr ? packed_out : &unused;
-  *packed = 0;
-  try {
-    MarkedPlan plan;
-    const int status =
-        xts_plan(src, src_offset, length, granule, bitmap, key, key_len,
-                 first_unit, staging_bytes, static_cast<bool>(sink), &plan);
-    if (status != kIoOk || plan.marked == 0) return status;
-    const XtsSchedules schedules(key);
-    const int device = granule_kernel_device(src, src);
-    if (device < 0) {
-      return xts_pack_generic(src, src_offset, length, granule, bitmap,
-                              schedules, first_unit, staging_bytes, sink,
-                              packed);
-    }
-    XtsStream xs(device, src, src_offset, granule, plan, schedules, true,
-                 first_unit);
-    return xts_pack_gpu(xs, plan, sink, packed);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
+                              const XtsKey& key, uint64_t staging_bytes,
+                              const PackSink& sink, uint64_t* packed) {
+  return xts_marked_sync(src, src_offset, length, granule, bitmap, key,
+                         staging_bytes, sink, packed);
 }
 
 int bdev_xts_unpack_marked_sync(Bdev* dst, uint64_t dst_offset,
                                 uint64_t length, uint32_t granule,
                                 const std::vector<uint64_t>& bitmap,
-                                const uint8_t* key, size_t key_len,
-                                uint64_t first_unit, uint64_t staging_bytes,
+                                const XtsKey& key, uint64_t staging_bytes,
                                 const UnpackSource& source,
-                                uint64_t* unpacked_out) {
-  uint64_t unused = 0;
-  uint64_t* unpacked = unpacked_out != nullptr ? unpacked_out : &unused;
-  *unpacked = 0;
-  try {
-    MarkedPlan plan;
-    const int status =
-        xts_plan(dst, dst_offset, length, granule, bitmap, key, key_len,
-                 first_unit, staging_bytes, static_cast<bool>(source), &plan);
-    if (status != kIoOk || plan.marked == 0) return status;
-    const XtsSchedules schedules(key);
-    const int device = granule_kernel_device(dst, dst);
-    if (device < 0) {
-      return xts_unpack_generic(dst, dst_offset, length, granule, bitmap,
-                                schedules, first_unit, staging_bytes, source,
-                                unpacked);
-    }
-    XtsStream xs(device, dst, dst_offset, granule, plan, schedules, false,
-                 first_unit);
-    return xts_unpack_gpu(xs, plan, source, unpacked);
-  } catch (const std::exception&) {
-    return kIoFailed;
-  }
+                                uint64_t* unpacked) {
+  return xts_marked_sync(dst, dst_offset, length, granule, bitmap, key,
+                         staging_bytes, source, unpacked);
 }
 
 }  // namespace hipstore

@@ -27,27 +27,48 @@ static_assert(kDeltaHeaderBytes == kHeaderBytes &&
                   kDeltaTrailerBytes == kTrailerBytes,
               "delta.h documents the core's header and trailer");
 
-const Format kDelta = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
-                       {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
-                       kDeltaVersion, "delta file"};
-const Format kDeltaLz = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
-                         {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
-                         kDeltaVersionLz, "delta file"};
-const Format kDeltaXts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
-                          {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
-                          kDeltaVersionXts, "delta file"};
-const Format kDeltaDict = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
-                           {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
-                           kDeltaVersionDict, "delta file"};
-const Format kDeltaCts = {{'H', 'S', 'D', 'E', 'L', 'T', 'A', '1'},
-                          {'H', 'S', 'D', 'E', 'N', 'D', '1', '\0'},
-                          kDeltaVersionCts, "delta file"};
-const Format kMap = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
-                     {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
-                     kFingerprintMapVersion, "fingerprint map"};
-const Format kMapBlake2s2 = {{'H', 'S', 'F', 'P', 'M', 'A', 'P', '1'},
-                             {'H', 'S', 'F', 'P', 'E', 'N', 'D', '1'},
-                             kFingerprintMapVersionBlake2s, "fingerprint map"};
+// The versions of a format differ in the version alone. The magics are
+// eight bytes; a shorter literal is padded with NULs.
+Format make_format(const char* magic, const char* end_magic, uint32_t version,
+                   const char* noun) {
+  Format f = {{0}, {0}, version, noun};
+  strncpy(f.magic, magic, sizeof(f.magic));
+  strncpy(f.end_magic, end_magic, sizeof(f.end_magic));
+  return f;
+}
+
+Format delta_format(uint32_t version) {
+  return make_format("HSDELTA1", "HSDEND1", version, "delta file");
+}
+
+Format map_format(uint32_t version) {
+  return make_format("HSFPMAP1", "HSFPEND1", version, "fingerprint map");
+}
+
+// Indexed by version - 1.
+const Format kDeltaFormats[] = {
+    delta_format(kDeltaVersion), delta_format(kDeltaVersionLz),
+    delta_format(kDeltaVersionXts), delta_format(kDeltaVersionDict),
+    delta_format(kDeltaVersionCts)};
+const Format kMap = map_format(kFingerprintMapVersion);
+const Format kMapBlake2s2 = map_format(kFingerprintMapVersionBlake2s);
+
+// The version of a file with these properties. A dictionary needs
+// compression; compressed and encrypted is version 5 with or without one.
+uint32_t delta_version(bool compressed, bool dictionary, bool encrypted) {
+  if (compressed && encrypted) return kDeltaVersionCts;
+  if (dictionary) return kDeltaVersionDict;
+  if (compressed) return kDeltaVersionLz;
+  return encrypted ? kDeltaVersionXts : kDeltaVersion;
+}
+
+// Header bytes 20-23 of such a file.
+uint32_t delta_flags(const DeltaInfo& info) {
+  return (info.full ? kDeltaFlagFull : 0) |
+         (info.compressed ? kDeltaFlagLz : 0) |
+         (info.dictionary ? kDeltaFlagDict : 0) |
+         (info.encrypted ? kDeltaFlagXts : 0);
+}
 
 const char kBadGranule[] =
     "invalid granule (a multiple of the block size and of 16 that divides "
@@ -116,8 +137,9 @@ int parse_delta(const std::string& path, ParsedDelta* out,
                 std::string* error) {
   InFile& in = out->in;
   int status =
-      in.open(path, kDelta, error,
-              {&kDeltaLz, &kDeltaXts, &kDeltaDict, &kDeltaCts});
+      in.open(path, kDeltaFormats[0], error,
+              {&kDeltaFormats[1], &kDeltaFormats[2], &kDeltaFormats[3],
+               &kDeltaFormats[4]});
   if (status != kIoOk) return status;
   const Header& h = in.header;
   DeltaInfo& info = out->info;
@@ -136,13 +158,10 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   info.n_granules = h.n_granules;
   info.n_marked = get_u64(h.owned);
   info.file_bytes = in.file_bytes;
-  // The spare words: version 1 none, versions 2, 4 and 5 both, version 3
-  // the first.
-  if ((h.word & ~(kDeltaFlagFull | kDeltaFlagLz | kDeltaFlagXts |
-                  kDeltaFlagDict)) != 0 ||
-      ((h.word & kDeltaFlagLz) != 0) != info.compressed ||
-      ((h.word & kDeltaFlagDict) != 0) != info.dictionary ||
-      ((h.word & kDeltaFlagXts) != 0) != info.encrypted ||
+  // The flag word is exactly what the version stands for: no unknown bit,
+  // and each known one as the version says. The spare words: version 1
+  // none, versions 2, 4 and 5 both, version 3 the first.
+  if (h.word != delta_flags(info) ||
       (!info.compressed && get_u32(h.owned + 16) != 0) ||
       (!info.compressed && !info.encrypted && get_u32(h.owned + 12) != 0)) {
     return fail(error, kIoInvalid, "unknown flags or non-zero reserved field");
@@ -214,123 +233,98 @@ int parse_delta(const std::string& path, ParsedDelta* out,
   return in.check_trailer(info.n_marked, error);
 }
 
-// The version-2 file: as write_delta, with the granules compressed
-// (bdev_compress_marked_sync) and record_area_bytes put into the header
-// once the records are out. With info->dictionary the version-4 file:
-// the same, compressed against `base` (bdev_dict_compress_marked_sync).
-// With `key` (info->encrypted) the version-5 file: the key block follows
-// the bitmap and the records hold what the keyed calls deliver, every
-// piece in max(size, 16) bytes.
-int write_delta_lz(OutFile* out, Bdev* src, Bdev* base,
-                   const std::vector<uint64_t>& bitmap,
-                   const std::vector<uint8_t>* key, DeltaInfo* info,
-                   std::string* error) {
-  const uint32_t min_piece = info->encrypted ? 16 : 1;
+// The marked calls' key argument for a file's records: unit 0 is granule
+// 0 of the volume. No key for a file that is not encrypted.
+XtsKey record_key(const DeltaInfo& info, const std::vector<uint8_t>* key) {
+  if (!info.encrypted) return {};
+  return {key->data(), key->size(), 0};
+}
+
+// Header, bitmap, the marked granules of `src` as records, trailer, all
+// synced. Fills info->file_bytes and info->stored_bytes. The records are
+// fixed (versions 1 and 3: bdev_pack_marked_sync, or with `key`, which
+// info->encrypted goes with, what bdev_xts_pack_marked_sync delivers, and
+// the key check value in the header) or variable (info->compressed,
+// versions 2, 4 and 5: bdev_compress_marked_sync, with info->dictionary
+// against `base`, and record_area_bytes put into the header once the
+// records are out). A compressed file with `key` is version 5: the key
+// block follows the bitmap and the records hold what the keyed calls
+// deliver, every piece in max(size, 16) bytes.
+int write_delta(OutFile* out, Bdev* src, Bdev* base,
+                const std::vector<uint64_t>& bitmap,
+                const std::vector<uint8_t>* key, DeltaInfo* info,
+                std::string* error) {
+  const bool key_block = info->compressed && info->encrypted;
   std::vector<uint8_t> raw(bitmap.size() * 8);
   for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
-  Header h = {info->block_size, info->granule,
-              (info->full ? kDeltaFlagFull : 0) | kDeltaFlagLz |
-                  (info->dictionary ? kDeltaFlagDict : 0) |
-                  (info->encrypted ? kDeltaFlagXts : 0),
+  Header h = {info->block_size, info->granule, delta_flags(*info),
               info->volume_bytes, info->n_granules, {0}};
   put_u64(h.owned, info->n_marked);
   put_u32(h.owned + 8, crc32c_sw(0, raw.data(), raw.size()));
-  int status = out->begin(info->encrypted    ? kDeltaCts
-                          : info->dictionary ? kDeltaDict
-                                             : kDeltaLz,
-                          h, error);
+  uint8_t block[kKeyBlockBytes];
+  if (key_block) {
+    put_key_block(block, xts_kcv(key->data()));
+  } else if (info->encrypted) {
+    put_u32(h.owned + 12, xts_kcv(key->data()));
+  }
+  int status = out->begin(kDeltaFormats[info->version - 1], h, error);
   if (status != kIoOk) return status;
-  VarRecordWriter writer(out, info->granule, record_granules(info->granule),
-                         info->n_marked, min_piece);
-  uint8_t key_block[kKeyBlockBytes];
-  if (info->encrypted) put_key_block(key_block, xts_kcv(key->data()));
+  info->stored_bytes = info->n_marked * info->granule;
   if (out->write(raw.data(), raw.size()) &&  // else end() reports it
-      (!info->encrypted || out->write(key_block, sizeof(key_block)))) {
+      (!key_block || out->write(block, sizeof(block)))) {
+    const XtsKey xts = record_key(*info, key);
     uint64_t packed = 0;
+    bool complete = false;
     std::string why;
-    const CompressSink sink = [&writer, min_piece](const uint8_t* data,
-                                                   const uint32_t* sizes,
-                                                   uint64_t, uint64_t count) {
-      int added = kIoOk;
-      for (uint64_t i = 0; i < count && added == kIoOk; ++i) {
-        added = writer.add(data, sizes[i]);
-        data += lz_padded(std::max(sizes[i], min_piece));
-      }
-      return added;
-    };
-    const uint8_t* raw_key = info->encrypted ? key->data() : nullptr;
-    const size_t key_len = info->encrypted ? key->size() : 0;
-    status = info->dictionary
-                 ? bdev_dict_compress_marked_sync(src, 0, base, 0,
-                                                  info->volume_bytes,
-                                                  info->granule, bitmap, 0,
-                                                  sink, &packed, &why, raw_key,
-                                                  key_len, 0)
-                 : bdev_compress_marked_sync(src, 0, info->volume_bytes,
-                                             info->granule, bitmap, 0, sink,
-                                             &packed, &why, raw_key, key_len,
-                                             0);
-    if (status != kIoOk || packed != info->n_marked || !writer.complete()) {
+    if (info->compressed) {
+      const uint32_t min_piece = info->encrypted ? 16 : 1;
+      VarRecordWriter writer(out, info->granule,
+                             record_granules(info->granule), info->n_marked,
+                             min_piece);
+      LzOptions options;
+      options.key = xts;
+      if (info->dictionary) options.base = base;
+      status = bdev_compress_marked_sync(
+          src, 0, info->volume_bytes, info->granule, bitmap, options,
+          [&writer, min_piece](const uint8_t* data, const uint32_t* sizes,
+                               uint64_t, uint64_t count) {
+            int added = kIoOk;
+            for (uint64_t i = 0; i < count && added == kIoOk; ++i) {
+              added = writer.add(data, sizes[i]);
+              data += lz_padded(std::max(sizes[i], min_piece));
+            }
+            return added;
+          },
+          &packed, &why);
+      complete = writer.complete();
+      put_u64(h.owned + 12, writer.area());
+      info->stored_bytes = writer.unit_bytes();
+    } else {
+      RecordWriter writer(out, info->granule, record_granules(info->granule),
+                          info->n_marked);
+      const PackSink sink = [&writer](const uint8_t* data, uint64_t,
+                                      uint64_t count) {
+        return writer.add(data, count);
+      };
+      status = info->encrypted
+                   ? bdev_xts_pack_marked_sync(src, 0, info->volume_bytes,
+                                               info->granule, bitmap, xts, 0,
+                                               sink, &packed)
+                   : bdev_pack_marked_sync(src, 0, info->volume_bytes,
+                                           info->granule, bitmap, 0, sink,
+                                           &packed);
+      complete = writer.complete();
+    }
+    if (status != kIoOk || packed != info->n_marked || !complete) {
       if (why.empty()) {
         why = "reading the volume or writing " + out->tmp() + " failed";
       }
       return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed, why);
     }
-    put_u64(h.owned + 12, writer.area());
-    out->rewrite_header(h);
+    if (info->compressed) out->rewrite_header(h);
   }
   status = out->end(info->n_marked, error);
   info->file_bytes = out->bytes();
-  info->stored_bytes = writer.unit_bytes();
-  return status;
-}
-
-// Header, bitmap, the marked granules of `src` as records, trailer, all
-// synced. Fills info->file_bytes and info->stored_bytes. With `key`
-// (info->encrypted) the records hold what bdev_xts_pack_marked_sync
-// delivers and the header the key check value.
-int write_delta(OutFile* out, Bdev* src, Bdev* base,
-                const std::vector<uint64_t>& bitmap,
-                const std::vector<uint8_t>* key, DeltaInfo* info,
-                std::string* error) {
-  if (info->compressed) {
-    return write_delta_lz(out, src, base, bitmap, key, info, error);
-  }
-  std::vector<uint8_t> raw(bitmap.size() * 8);
-  for (size_t w = 0; w < bitmap.size(); ++w) put_u64(&raw[w * 8], bitmap[w]);
-  Header h = {info->block_size, info->granule,
-              (info->full ? kDeltaFlagFull : 0) |
-                  (info->encrypted ? kDeltaFlagXts : 0),
-              info->volume_bytes, info->n_granules, {0}};
-  put_u64(h.owned, info->n_marked);
-  put_u32(h.owned + 8, crc32c_sw(0, raw.data(), raw.size()));
-  if (info->encrypted) put_u32(h.owned + 12, xts_kcv(key->data()));
-  int status = out->begin(info->encrypted ? kDeltaXts : kDelta, h, error);
-  if (status != kIoOk) return status;
-  if (out->write(raw.data(), raw.size())) {  // else end() reports it
-    RecordWriter writer(out, info->granule, record_granules(info->granule),
-                        info->n_marked);
-    uint64_t packed = 0;
-    const PackSink sink = [&writer](const uint8_t* data, uint64_t,
-                                    uint64_t count) {
-      return writer.add(data, count);
-    };
-    status = info->encrypted
-                 ? bdev_xts_pack_marked_sync(src, 0, info->volume_bytes,
-                                             info->granule, bitmap,
-                                             key->data(), key->size(), 0, 0,
-                                             sink, &packed)
-                 : bdev_pack_marked_sync(src, 0, info->volume_bytes,
-                                         info->granule, bitmap, 0, sink,
-                                         &packed);
-    if (status != kIoOk || packed != info->n_marked || !writer.complete()) {
-      return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
-                  "reading the volume or writing " + out->tmp() + " failed");
-    }
-  }
-  status = out->end(info->n_marked, error);
-  info->file_bytes = out->bytes();
-  info->stored_bytes = info->n_marked * info->granule;
   return status;
 }
 
@@ -576,92 +570,122 @@ int mark_all(Bdev* src, uint32_t granule, Marked* out, std::string* error) {
   return kIoOk;
 }
 
-// The record pass of a version-2 or version-4 import. dry_run validates
-// every piece here; otherwise bdev_decompress_marked_sync (version 4:
-// bdev_dict_decompress_marked_sync, whose dictionaries are the target's
-// granules) does, before it decodes. A version-5 file's pieces are
-// ciphertext in max(size, 16) bytes each: dry_run checks records and sizes
-// and, given the key, decrypts and validates every piece; otherwise the
-// keyed calls validate, on the GPU while decoding or on the host.
-int import_lz(Bdev* dst, ParsedDelta* file, bool dry_run,
-              const std::vector<uint8_t>* key, std::string* error) {
-  const DeltaInfo& info = file->info;
-  const uint32_t min_piece = info.encrypted ? 16 : 1;
-  VarRecordReader reader(&file->in, file->records_offset, file->record_area,
-                         info.granule, record_granules(info.granule),
-                         info.n_marked, min_piece);
-  std::string why;
-  int status = kIoOk;
+// The dry run over the variable records of a compressed file: every
+// piece is validated here. A version-5 file's pieces are ciphertext in
+// max(size, 16) bytes each: without the key only records and sizes are
+// checked, with it every piece is decrypted and validated.
+int check_pieces(const ParsedDelta& file, VarRecordReader* reader,
+                 const std::vector<uint8_t>* key, std::string* why) {
+  const DeltaInfo& info = file.info;
+  std::unique_ptr<XtsSchedules> keys;
+  if (info.encrypted && key != nullptr) {
+    keys.reset(new XtsSchedules(key->data()));
+  }
+  std::vector<uint8_t> plain(info.granule);
   const uint8_t* piece = nullptr;
   uint32_t size = 0;
-  if (dry_run) {
-    std::unique_ptr<XtsSchedules> keys;
-    if (info.encrypted && key != nullptr) {
-      keys.reset(new XtsSchedules(key->data()));
-    }
-    std::vector<uint8_t> plain(info.granule);
-    for (uint64_t w = 0; w < file->bitmap.size() && status == kIoOk; ++w) {
-      for (uint64_t word = file->bitmap[w]; word != 0 && status == kIoOk;
-           word &= word - 1) {
-        status = reader.next(&piece, &size, &why);
-        if (info.encrypted) {
-          if (keys == nullptr) continue;  // structure and CRCs only
-          if (status != kIoOk) break;
-          xts_decrypt_var(*keys,
-                          w * 64 + static_cast<uint64_t>(__builtin_ctzll(word)),
-                          piece, plain.data(), std::max(size, 16u));
-          piece = plain.data();
-        }
-        std::string rule;
-        if (status == kIoOk &&
-            !(info.dictionary
-                  ? lz_dict_validate_granule(piece, size, info.granule, &rule)
-                  : lz_validate_granule(piece, size, info.granule, &rule))) {
-          status = kIoInvalid;
-          why = "granule " +
-                std::to_string(w * 64 +
-                               static_cast<uint64_t>(__builtin_ctzll(word))) +
-                ": bad compressed piece (" + rule + ")";
-        }
+  int status = kIoOk;
+  for (uint64_t w = 0; w < file.bitmap.size() && status == kIoOk; ++w) {
+    for (uint64_t word = file.bitmap[w]; word != 0 && status == kIoOk;
+         word &= word - 1) {
+      const uint64_t g = w * 64 + static_cast<uint64_t>(__builtin_ctzll(word));
+      status = reader->next(&piece, &size, why);
+      if (info.encrypted) {
+        if (keys == nullptr) continue;  // structure and CRCs only
+        if (status != kIoOk) break;
+        xts_decrypt_var(*keys, g, piece, plain.data(), std::max(size, 16u));
+        piece = plain.data();
       }
-    }
-    if (status != kIoOk) return fail(error, status, why);
-  } else if (info.n_marked > 0) {
-    uint64_t applied = 0;
-    const DecompressSource source = [&](uint8_t* data, uint32_t* sizes,
-                                        uint64_t, uint64_t count) {
-      for (uint64_t i = 0; i < count; ++i) {
-        const int got = reader.next(&piece, &size, &why);
-        if (got != kIoOk) return got;
-        sizes[i] = size;
-        const uint32_t stored = std::max(size, min_piece);
-        memcpy(data, piece, stored);
-        memset(data + stored, 0, lz_padded(stored) - stored);
-        data += lz_padded(stored);
+      std::string rule;
+      if (status == kIoOk &&
+          !(info.dictionary
+                ? lz_dict_validate_granule(piece, size, info.granule, &rule)
+                : lz_validate_granule(piece, size, info.granule, &rule))) {
+        status = kIoInvalid;
+        *why = "granule " + std::to_string(g) + ": bad compressed piece (" +
+               rule + ")";
       }
-      return static_cast<int>(kIoOk);
-    };
-    const uint8_t* raw_key = info.encrypted ? key->data() : nullptr;
-    const size_t key_len = info.encrypted ? key->size() : 0;
-    status = info.dictionary
-                 ? bdev_dict_decompress_marked_sync(dst, 0, info.volume_bytes,
-                                                    info.granule, file->bitmap,
-                                                    0, source, &applied, &why,
-                                                    raw_key, key_len, 0)
-                 : bdev_decompress_marked_sync(dst, 0, info.volume_bytes,
-                                               info.granule, file->bitmap, 0,
-                                               source, &applied, &why, raw_key,
-                                               key_len, 0);
-    if (status != kIoOk) {
-      if (why.empty()) why = "writing the target failed";
-      return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
-                  why + "; " + std::to_string(applied) + " of " +
-                      std::to_string(info.n_marked) +
-                      " granules were applied, the target may be partly "
-                      "updated");
     }
   }
-  if (reader.left() != 0) {
+  return status;
+}
+
+// The record pass of an import. dry_run checks every record and writes
+// nothing: the fixed records by their CRCs, the variable ones in
+// check_pieces. Otherwise the marked calls apply them: fixed records
+// through bdev_unpack_marked_sync or, encrypted, bdev_xts_unpack_marked_sync;
+// compressed pieces through bdev_decompress_marked_sync, which validates
+// each before it decodes (a version-4 file's dictionaries are the target's
+// granules; a version-5 file's pieces are validated on the GPU while
+// decoding, or on the host).
+int import_records(Bdev* dst, ParsedDelta* file, bool dry_run,
+                   const std::vector<uint8_t>* key, std::string* error) {
+  const DeltaInfo& info = file->info;
+  const bool apply = !dry_run && info.n_marked > 0;
+  std::string why;
+  uint64_t applied = 0;
+  uint64_t left = 0;
+  int status = kIoOk;
+  if (info.compressed) {
+    const uint32_t min_piece = info.encrypted ? 16 : 1;
+    VarRecordReader reader(&file->in, file->records_offset, file->record_area,
+                           info.granule, record_granules(info.granule),
+                           info.n_marked, min_piece);
+    if (dry_run) {
+      status = check_pieces(*file, &reader, key, &why);
+    } else if (apply) {
+      const DecompressSource source = [&](uint8_t* data, uint32_t* sizes,
+                                          uint64_t, uint64_t count) {
+        const uint8_t* piece = nullptr;
+        for (uint64_t i = 0; i < count; ++i) {
+          const int got = reader.next(&piece, &sizes[i], &why);
+          if (got != kIoOk) return got;
+          const uint32_t stored = std::max(sizes[i], min_piece);
+          memcpy(data, piece, stored);
+          memset(data + stored, 0, lz_padded(stored) - stored);
+          data += lz_padded(stored);
+        }
+        return static_cast<int>(kIoOk);
+      };
+      LzOptions options;
+      options.key = record_key(info, key);
+      options.dictionary = info.dictionary;
+      status = bdev_decompress_marked_sync(dst, 0, info.volume_bytes,
+                                           info.granule, file->bitmap, options,
+                                           source, &applied, &why);
+    }
+    left = reader.left();
+  } else {
+    RecordReader reader(&file->in, file->records_offset, info.granule,
+                        record_granules(info.granule), info.n_marked);
+    if (dry_run) {
+      status = reader.take(nullptr, info.n_marked, &why);
+    } else if (apply) {
+      const UnpackSource source = [&reader, &why](uint8_t* data, uint64_t,
+                                                  uint64_t count) {
+        return reader.take(data, count, &why);
+      };
+      status = info.encrypted
+                   ? bdev_xts_unpack_marked_sync(dst, 0, info.volume_bytes,
+                                                 info.granule, file->bitmap,
+                                                 record_key(info, key), 0,
+                                                 source, &applied)
+                   : bdev_unpack_marked_sync(dst, 0, info.volume_bytes,
+                                             info.granule, file->bitmap, 0,
+                                             source, &applied);
+    }
+    left = reader.left();
+  }
+  if (status != kIoOk && dry_run) return fail(error, status, why);
+  if (status != kIoOk) {
+    if (why.empty()) why = "writing the target failed";
+    return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
+                why + "; " + std::to_string(applied) + " of " +
+                    std::to_string(info.n_marked) +
+                    " granules were applied, the target may be partly "
+                    "updated");
+  }
+  if (left != 0) {
     return fail(error, kIoInvalid, "records left over after the last granule");
   }
   return kIoOk;
@@ -744,11 +768,7 @@ int bdev_export_delta(Bdev* src, Bdev* base, const std::string& path,
     return fail(error, kIoInvalid, "a key needs granule <= 16777216");
   }
   DeltaInfo info;
-  info.version = cts             ? kDeltaVersionCts
-                 : dictionary    ? kDeltaVersionDict
-                 : compress      ? kDeltaVersionLz
-                 : key != nullptr ? kDeltaVersionXts
-                                  : kDeltaVersion;
+  info.version = delta_version(compress, dictionary, key != nullptr);
   info.compressed = compress;
   info.dictionary = dictionary;
   info.encrypted = key != nullptr;
@@ -838,45 +858,9 @@ int bdev_import_delta(Bdev* dst, const std::string& path, bool dry_run,
                 "bdev " + dst->name() +
                     " is claimed; import runs offline only");
   }
-  if (info.compressed) {
-    status = import_lz(dst, &file, dry_run, key, error);
-    if (status == kIoOk && stats != nullptr) *stats = info;
-    return status;
-  }
-  RecordReader reader(&file.in, file.records_offset, info.granule,
-                      record_granules(info.granule), info.n_marked);
-  std::string why;
-  if (dry_run) {
-    status = reader.take(nullptr, info.n_marked, &why);
-    if (status != kIoOk) return fail(error, status, why);
-  } else if (info.n_marked > 0) {
-    uint64_t applied = 0;
-    const UnpackSource source = [&reader, &why](uint8_t* data, uint64_t,
-                                                uint64_t count) {
-      return reader.take(data, count, &why);
-    };
-    status = info.encrypted
-                 ? bdev_xts_unpack_marked_sync(dst, 0, info.volume_bytes,
-                                               info.granule, file.bitmap,
-                                               key->data(), key->size(), 0, 0,
-                                               source, &applied)
-                 : bdev_unpack_marked_sync(dst, 0, info.volume_bytes,
-                                           info.granule, file.bitmap, 0,
-                                           source, &applied);
-    if (status != kIoOk) {
-      if (why.empty()) why = "writing the target failed";
-      return fail(error, status == kIoInvalid ? kIoInvalid : kIoFailed,
-                  why + "; " + std::to_string(applied) + " of " +
-                      std::to_string(info.n_marked) +
-                      " granules were applied, the target may be partly "
-                      "updated");
-    }
-  }
-  if (reader.left() != 0) {
-    return fail(error, kIoInvalid, "records left over after the last granule");
-  }
-  if (stats != nullptr) *stats = info;
-  return kIoOk;
+  status = import_records(dst, &file, dry_run, key, error);
+  if (status == kIoOk && stats != nullptr) *stats = info;
+  return status;
 }
 
 int bdev_fingerprint_file(Bdev* bdev, const std::string& path,

@@ -1308,7 +1308,7 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         // clone, to a delta file (HBM volumes leave through
         // k_pack_marked, one launch per staging window; with "compress"
         // through k_lz_compress_marked and k_gather_var, with "dictionary"
-        // too through k_lzd_compress_marked, with "key_file" through
+        // too through k_lz_compress_marked<true>, with "key_file" through
         // k_xts_pack_marked; with "cts", "compress" and "key_file" through
         // the compress kernels and k_xts_var).
         const std::string name = p.get_string("name");

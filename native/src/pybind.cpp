@@ -205,6 +205,10 @@ struct KeyArg {
     if (!bytes.empty()) explicit_bzero(bytes.data(), bytes.size());
   }
   const std::vector<uint8_t>* ptr() const { return given ? &bytes : nullptr; }
+  // For the marked calls; None is no key.
+  XtsKey xts(uint64_t first_unit) const {
+    return {given ? bytes.data() : nullptr, bytes.size(), first_unit};
+  }
 };
 
 // Marks of `words` below granule n_granules.
@@ -831,8 +835,8 @@ PYBIND11_MODULE(_hipstore, m) {
     delta_call("bdev_xts_pack_marked", [&](std::string* error) {
       *error = "bad key, granule, range or first_unit, or the pack failed";
       return bdev_xts_pack_marked_sync(
-          src.get(), src_offset, len, granule, words, key_arg.bytes.data(),
-          key_arg.bytes.size(), first_unit, staging_bytes,
+          src.get(), src_offset, len, granule, words, key_arg.xts(first_unit),
+          staging_bytes,
           [&out, granule](const uint8_t* data, uint64_t, uint64_t count) {
             out.append(reinterpret_cast<const char*>(data), count * granule);
             return 0;
@@ -866,8 +870,8 @@ PYBIND11_MODULE(_hipstore, m) {
     delta_call("bdev_xts_unpack_marked", [&](std::string* error) {
       *error = "bad key, granule, range or first_unit, or the unpack failed";
       return bdev_xts_unpack_marked_sync(
-          dst.get(), dst_offset, len, granule, words, key_arg.bytes.data(),
-          key_arg.bytes.size(), first_unit, staging_bytes,
+          dst.get(), dst_offset, len, granule, words, key_arg.xts(first_unit),
+          staging_bytes,
           [&dense, granule](uint8_t* out, uint64_t first_rank,
                             uint64_t count) {
             memcpy(out, dense.data() + first_rank * granule, count * granule);
@@ -914,7 +918,7 @@ PYBIND11_MODULE(_hipstore, m) {
      "The stored form of one granule: an LZ4 block, or the granule itself "
      "when that would not be smaller (host codec, the byte model of "
      "k_lz_compress_marked); with `dictionary` (as long as the data) the "
-     "HSLZD1 form, the byte model of k_lzd_compress_marked");
+     "HSLZD1 form, the byte model of k_lz_compress_marked<true>");
 
   m.def("lz_decompress_granule", [](py::bytes piece, uint32_t granule,
                                     std::optional<py::bytes> dictionary) {
@@ -982,16 +986,15 @@ PYBIND11_MODULE(_hipstore, m) {
       return 0;
     };
     delta_call("bdev_compress_marked", [&](std::string* error) {
-      return base ? bdev_dict_compress_marked_sync(
-                        src.get(), src_offset, base->get(), base_offset, len,
-                        granule, words, staging_bytes, sink, nullptr, error,
-                        key_arg.given ? key_arg.bytes.data() : nullptr,
-                        key_arg.bytes.size(), first_unit)
-                  : bdev_compress_marked_sync(
-                        src.get(), src_offset, len, granule, words,
-                        staging_bytes, sink, nullptr, error,
-                        key_arg.given ? key_arg.bytes.data() : nullptr,
-                        key_arg.bytes.size(), first_unit);
+      LzOptions options;
+      options.staging_bytes = staging_bytes;
+      options.key = key_arg.xts(first_unit);
+      if (base) {
+        options.base = base->get();
+        options.base_offset = base_offset;
+      }
+      return bdev_compress_marked_sync(src.get(), src_offset, len, granule,
+                                       words, options, sink, nullptr, error);
     });
     return py::make_tuple(sizes, py::bytes(out));
   }, py::arg("src"), py::arg("bitmap"), py::arg("granule"),
@@ -1052,20 +1055,14 @@ PYBIND11_MODULE(_hipstore, m) {
       }
       return 0;
     };
-    const uint8_t* key_ptr = key_arg.given ? key_arg.bytes.data() : nullptr;
     delta_call("bdev_decompress_marked", [&](std::string* error) {
-      return dictionary
-                 ? bdev_dict_decompress_marked_sync(dst.get(), dst_offset, len,
-                                                    granule, words,
-                                                    staging_bytes, source,
-                                                    &unpacked, error, key_ptr,
-                                                    key_arg.bytes.size(),
-                                                    first_unit)
-                 : bdev_decompress_marked_sync(dst.get(), dst_offset, len,
-                                               granule, words, staging_bytes,
-                                               source, &unpacked, error,
-                                               key_ptr, key_arg.bytes.size(),
-                                               first_unit);
+      LzOptions options;
+      options.staging_bytes = staging_bytes;
+      options.key = key_arg.xts(first_unit);
+      options.dictionary = dictionary;
+      return bdev_decompress_marked_sync(dst.get(), dst_offset, len, granule,
+                                         words, options, source, &unpacked,
+                                         error);
     });
     return unpacked;
   }, py::arg("dst"), py::arg("bitmap"), py::arg("granule"), py::arg("sizes"),
@@ -1094,13 +1091,11 @@ PYBIND11_MODULE(_hipstore, m) {
       const auto t0 = std::chrono::steady_clock::now();
       const int status =
           unpack ? bdev_xts_unpack_marked_sync(
-                       bdev.get(), 0, len, granule, words,
-                       key_arg.bytes.data(), key_arg.bytes.size(), 0,
+                       bdev.get(), 0, len, granule, words, key_arg.xts(0),
                        staging_bytes,
                        [](uint8_t*, uint64_t, uint64_t) { return 0; }, &moved)
                  : bdev_xts_pack_marked_sync(
-                       bdev.get(), 0, len, granule, words,
-                       key_arg.bytes.data(), key_arg.bytes.size(), 0,
+                       bdev.get(), 0, len, granule, words, key_arg.xts(0),
                        staging_bytes,
                        [](const uint8_t*, uint64_t, uint64_t) { return 0; },
                        &moved);
