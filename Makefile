@@ -105,7 +105,8 @@ submit-path-test: $(B)/submit_path_test $(B)/submit_path_test_tsan
 # Stand-alone check of the parity host code (GF(2^8) tables, rebuild
 # coefficients, the generic path on malloc bdevs) under AddressSanitizer:
 # host code only, needs no GPU.
-PARITY_TEST_SRCS := tests/native/parity_test.cpp native/src/parity.cpp native/src/bdev.cpp
+PARITY_TEST_SRCS := tests/native/parity_test.cpp tests/native/parity_update_stub.cpp \
+                    native/src/parity.cpp native/src/bdev.cpp
 
 $(B)/parity_test_asan: $(PARITY_TEST_SRCS) $(HDRS) | $(B)
 	$(HIPCC) $(CXXFLAGS) $(subst -fsanitize,-Xarch_host -fsanitize,$(ASAN_FLAGS)) -pthread $(PARITY_TEST_SRCS) -o $@

@@ -1,7 +1,9 @@
-// P+Q parity across bdevs: encode, check (scrub) and rebuild as bulk
-// operations, SnapRAID-like: encode while a set of volumes is quiescent,
-// scrub whenever wanted, rebuild onto fresh volumes after a loss. There
-// is no live composite bdev here and no read-modify-write.
+// P+Q parity across bdevs: encode, check (scrub), rebuild and update as
+// bulk operations, SnapRAID-like: encode while a set of volumes is
+// quiescent, scrub whenever wanted, rebuild onto fresh volumes after a
+// loss, update from clones of the members' earlier state. There is no
+// live composite bdev here; the only read-modify-write of parity is the
+// update call, offline like the rest.
 //
 // Definitions (every path produces exactly these bytes):
 //   - Field: GF(2^8), polynomial x^8+x^4+x^3+x^2+1 (0x11D), generator
@@ -17,6 +19,24 @@
 //         A = g^(y-x) * d, B = g^-x * d,
 //         D_x = A * S_P ^ B * S_Q, D_y = S_P ^ D_x
 //     Lost parity is recomputed by an encode pass once the data is back.
+//   - Update: `bases` has one slot per data member, a bdev range or
+//     absent. A member with a base is tracked: its base holds the
+//     member's bytes as of the moment the stored parity was last right.
+//     At least one member is tracked; untracked members are taken as
+//     unchanged and are not read. Per byte position, over the tracked
+//     members i with d_i = D_i ^ B_i:
+//       P ^= XOR of the d_i,  Q ^= XOR of g^i * d_i
+//     Bit g of the result's bitmap is set iff some tracked member differs
+//     from its base anywhere in granule g, which is not "the parity delta
+//     is non-zero": three or more members can change so that both deltas
+//     cancel, and such a granule is still reported (and refreshed).
+//     Parity bytes of a granule whose bit is clear are not written. With
+//     `refresh`, a tracked member's bytes are also stored into its base
+//     wherever the two differ, so afterwards every base equals its member
+//     over the range and a second call is a no-op (0 granules, parity
+//     untouched). Without it the bases keep their bytes and a second call
+//     XORs the same deltas in again, which undoes the first: by
+//     definition, the caller re-clones or refreshes between cycles.
 //
 // When every member is HBM-resident, 16-byte aligned and reachable from
 // one device, the call runs on the GPU (parity_ops.hip: Horner form,
@@ -69,7 +89,7 @@ struct ParityReport {
   bool on_gpu = false;
 };
 
-// All three calls return IoStatus and never throw. kIoInvalid unless:
+// All four calls return IoStatus and never throw. kIoInvalid unless:
 // 1 <= k <= 32; P or Q given; all members share a block size; length is
 // non-zero and a multiple of the block size and of 16; offsets are
 // multiples of the block size; every range is in bounds; no bdev and no
@@ -109,6 +129,23 @@ int bdev_parity_rebuild_sync(const std::vector<ParityMember>& data,
                              const std::vector<int>& lost,
                              ParityReport* report = nullptr);
 
+// Brings the stored P and / or Q up to date from the tracked members and
+// their bases (definitions above); `changed` and `bitmap` have the layout
+// of bdev_diff_sync, tail bits 0, under the granule rules of the check
+// call. Also kIoInvalid unless bases.size() == k with at least one base
+// present, every base has the set's block size, a block-aligned offset
+// and its range in bounds, and no base shares a bdev or backing store
+// with a member, a parity or another base. A claimed P or Q, and with
+// `refresh` a claimed base, returns kIoFailed. Data members are only
+// read: claimed ones are allowed and advisory.
+int bdev_parity_update_sync(const std::vector<ParityMember>& data,
+                            ParityMember p, ParityMember q,
+                            const std::vector<ParityMember>& bases,
+                            uint64_t length, uint32_t granule,
+                            uint32_t max_report, bool refresh,
+                            DiffStats* changed, std::vector<uint64_t>* bitmap,
+                            ParityReport* report = nullptr);
+
 // Default extent of the RPC and Python front ends: what is left of the
 // shortest member after its offset, rounded down to a multiple of
 // `unit`; 0 when an offset lies past its device.
@@ -118,7 +155,8 @@ uint64_t parity_common_length(const std::vector<ParityMember>& data,
 // --- GPU path (parity_ops.hip); parity.cpp calls these after validation ---
 
 // Member base pointers with the offsets applied, by value in the kernel
-// arguments. A null slot is a lost member (rebuild only).
+// arguments. A null slot is a lost member (rebuild) or, in the bases of
+// an update, an untracked one.
 struct ParitySet {
   const uint8_t* data[kParityMaxData];
   uint32_t k;
@@ -140,5 +178,11 @@ int parity_check_gpu(int device, const ParitySet& set, const uint8_t* p,
 int parity_rebuild_gpu(int device, const ParitySet& set, const uint8_t* p,
                        const uint8_t* q, ParityCoeffs coeffs, uint8_t* out_a,
                        uint8_t* out_b, uint64_t length);
+// `bases`: slot i is member i's base or null, k as in `set`; written
+// only with `refresh`. Null `p` / `q`: that parity is not updated.
+int parity_update_gpu(int device, const ParitySet& set, const ParitySet& bases,
+                      uint8_t* p, uint8_t* q, uint64_t n_granules,
+                      uint32_t granule, bool refresh,
+                      std::vector<uint64_t>* words);
 
 }  // namespace hipstore

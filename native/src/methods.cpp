@@ -1232,6 +1232,70 @@ void register_storage_methods(RpcServer* server, bool use_hbm, int device,
         return Json(std::move(o));
       });
 
+  server->register_method(
+      "bdev_parity_update",
+      [&manager, parity_params, parity_error, uint_param, max_report_param,
+       indices_to_json](const Json& p) {
+        // Bring P / Q up to date from the tracked data volumes and the
+        // clones of their earlier state named in "bases" (null = not
+        // tracked); offline only for P, Q and, with "refresh", the bases.
+        const char* method = "bdev_parity_update";
+        uint64_t granule = uint_param(p, "granule", 0);
+        if (granule > UINT32_MAX) {
+          throw RpcError{kInvalidParams, "granule too large"};
+        }
+        ParityParams a = parity_params(method, p, granule);
+        if (granule == 0 && !a.data.empty()) {
+          granule = a.data[0].bdev->block_size();
+        }
+        const Json* list = p.get("bases");
+        if (list == nullptr || !list->is_array()) {
+          throw RpcError{kInvalidParams,
+                         std::string(method) +
+                             ": bases must be a list of bdev names or nulls"};
+        }
+        const uint64_t offset = uint_param(p, "offset", 0);
+        std::vector<ParityMember> bases;
+        for (const Json& name : list->as_array()) {
+          if (name.is_null()) {
+            bases.push_back(ParityMember{});
+            continue;
+          }
+          if (!name.is_string()) {
+            throw RpcError{kInvalidParams,
+                           std::string(method) +
+                               ": bases must be a list of bdev names or nulls"};
+          }
+          BdevPtr bdev = manager.find(name.as_string());
+          if (!bdev) not_found("bdev " + name.as_string());
+          a.hold.push_back(bdev);
+          bases.push_back(ParityMember{bdev.get(), offset});
+        }
+        if (!p.has("length")) {  // the bases bound the default extent too
+          std::vector<ParityMember> bound = a.data;
+          bound.insert(bound.end(), bases.begin(), bases.end());
+          a.length = parity_common_length(bound, a.p, a.q, granule);
+        }
+        ParityReport report;
+        DiffStats changed;
+        std::vector<uint64_t> bitmap;
+        const int status = bdev_parity_update_sync(
+            a.data, a.p, a.q, bases, a.length, static_cast<uint32_t>(granule),
+            max_report_param(p), p.get_bool("refresh", false), &changed,
+            &bitmap, &report);
+        if (status != kIoOk) throw parity_error(method, status, report);
+        JsonObject stats;
+        stats["granules"] = Json(static_cast<int64_t>(changed.granules));
+        stats["mismatched"] = Json(static_cast<int64_t>(changed.mismatched));
+        stats["first_mismatches"] = indices_to_json(changed.first_mismatches);
+        JsonObject o;
+        o["length"] = Json(static_cast<int64_t>(a.length));
+        o["granule"] = Json(static_cast<int64_t>(granule));
+        o["on_gpu"] = Json(report.on_gpu);
+        o["changed"] = Json(std::move(stats));
+        return Json(std::move(o));
+      });
+
   // --- checkpoints to files (native extensions) ----------------------------
   // kIoInvalid (parameters, geometry, malformed or corrupt file) is
   // -32602; everything else (I/O, claimed target, existing file) -32603.

@@ -1,5 +1,5 @@
 // P+Q parity across bdevs (hipstore/parity.h): the GF(2^8) tables, the
-// validation and path selection of the three calls, and their generic
+// validation and path selection of the four calls, and their generic
 // path through bdev_read_sync / bdev_write_sync.
 //
 // The generic path is a different algorithm from the kernels of
@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
+#include <utility>
 
 namespace hipstore {
 
@@ -144,6 +145,23 @@ int validate_set(const std::vector<ParityMember>& data, ParityMember p,
                     "a bdev or backing store appears twice in the set");
       }
     }
+  }
+  return kIoOk;
+}
+
+// The granule rules of the check and update calls.
+int validate_granule(uint64_t bs, uint64_t length, uint32_t granule,
+                     ParityReport* report) {
+  if (granule == 0 || granule % bs != 0 || granule % 16 != 0) {
+    return fail(report, kIoInvalid,
+                "granule must be a multiple of the block size and of 16");
+  }
+  if (length % granule != 0) {
+    return fail(report, kIoInvalid,
+                "length must be a multiple of the granule");
+  }
+  if (length / granule > kMaxGranules) {
+    return fail(report, kIoInvalid, "too many granules");
   }
   return kIoOk;
 }
@@ -325,6 +343,92 @@ int rebuild_generic(const std::vector<ParityMember>& survivors, ParityMember p,
   return kIoOk;
 }
 
+// Update from the bases (null bdev = untracked), span by span: the
+// deltas of the tracked members are summed with the tables, then XORed
+// into the stored parity wherever a member differed. `flags` has one
+// entry per piece of the span (a piece is the part of one granule inside
+// the span), so that parity is read and written in runs of dirty pieces
+// and never inside a granule whose bit stays clear.
+int update_generic(const std::vector<ParityMember>& data, ParityMember p,
+                   ParityMember q, const std::vector<ParityMember>& bases,
+                   uint64_t length, uint32_t granule, bool refresh,
+                   std::vector<uint64_t>* words) {
+  uint8_t* nw = span_bufs().get(0);
+  if (nw == nullptr) return kIoFailed;
+  uint8_t* old = span_bufs().get(1);
+  uint8_t* sum_p = p.bdev != nullptr ? span_bufs().get(2) : nullptr;
+  uint8_t* sum_q = q.bdev != nullptr ? span_bufs().get(3) : nullptr;
+  words->assign((length / granule + 63) / 64, 0);
+  const uint64_t span = span_bytes(data[0].bdev->block_size());
+  std::vector<uint8_t> flags;
+  uint8_t row[256];
+  for (uint64_t pos = 0; pos < length; pos += span) {
+    const uint64_t n = std::min(span, length - pos);
+    if (sum_p != nullptr) memset(sum_p, 0, n);
+    if (sum_q != nullptr) memset(sum_q, 0, n);
+    flags.clear();
+    for (size_t i = 0; i < data.size(); ++i) {
+      if (bases[i].bdev == nullptr) continue;
+      int status = bdev_read_sync(data[i].bdev, data[i].offset + pos, nw, n);
+      if (status == kIoOk) {
+        status = bdev_read_sync(bases[i].bdev, bases[i].offset + pos, old, n);
+      }
+      if (status != kIoOk) return status;
+      bool differs = false;
+      size_t piece_index = 0;
+      for (uint64_t off = 0; off < n; ++piece_index) {
+        const uint64_t g = (pos + off) / granule;
+        const uint64_t piece =
+            std::min<uint64_t>(granule - (pos + off) % granule, n - off);
+        if (piece_index == flags.size()) flags.push_back(0);
+        if (memcmp(nw + off, old + off, piece) != 0) {
+          flags[piece_index] = 1;
+          (*words)[g / 64] |= 1ull << (g % 64);
+          differs = true;
+        }
+        off += piece;
+      }
+      if (!differs) continue;
+      for (uint64_t b = 0; b < n; ++b) old[b] ^= nw[b];  // d_i
+      if (sum_p != nullptr) {
+        for (uint64_t b = 0; b < n; ++b) sum_p[b] ^= old[b];
+      }
+      if (sum_q != nullptr) {
+        mul_row(gf256_pow2(static_cast<int>(i)), row);
+        for (uint64_t b = 0; b < n; ++b) sum_q[b] ^= row[old[b]];
+      }
+      if (refresh) {
+        status = bdev_write_sync(bases[i].bdev, bases[i].offset + pos, nw, n);
+        if (status != kIoOk) return status;
+      }
+    }
+    // Runs of dirty pieces: stored ^= delta.
+    size_t piece_index = 0;
+    uint64_t run_start = 0;
+    bool in_run = false;
+    for (uint64_t off = 0; off <= n; ++piece_index) {
+      const bool dirty = off < n && flags[piece_index] != 0;
+      if (dirty && !in_run) run_start = off;
+      if (!dirty && in_run) {
+        const uint64_t run = off - run_start;
+        for (const auto& [parity, sum] : {std::pair{p, sum_p}, std::pair{q, sum_q}}) {
+          if (sum == nullptr) continue;
+          const uint64_t at = parity.offset + pos + run_start;
+          int status = bdev_read_sync(parity.bdev, at, nw, run);
+          if (status != kIoOk) return status;
+          for (uint64_t b = 0; b < run; ++b) nw[b] ^= sum[run_start + b];
+          status = bdev_write_sync(parity.bdev, at, nw, run);
+          if (status != kIoOk) return status;
+        }
+      }
+      in_run = dirty;
+      if (off == n) break;
+      off += std::min<uint64_t>(granule - (pos + off) % granule, n - off);
+    }
+  }
+  return kIoOk;
+}
+
 void fill_stats(const std::vector<uint64_t>& words, uint64_t n_granules,
                 uint32_t max_report, DiffStats* stats) {
   stats->granules = n_granules;
@@ -404,19 +508,10 @@ int bdev_parity_check_sync(const std::vector<ParityMember>& data,
     int status = validate_set(data, p, q, length, &all, report);
     if (status != kIoOk) return status;
     if (out == nullptr) return fail(report, kIoInvalid, "no result to fill");
-    const uint64_t bs = all[0].bdev->block_size();
-    if (granule == 0 || granule % bs != 0 || granule % 16 != 0) {
-      return fail(report, kIoInvalid,
-                  "granule must be a multiple of the block size and of 16");
-    }
-    if (length % granule != 0) {
-      return fail(report, kIoInvalid,
-                  "length must be a multiple of the granule");
-    }
+    status = validate_granule(all[0].bdev->block_size(), length, granule,
+                              report);
+    if (status != kIoOk) return status;
     const uint64_t n_granules = length / granule;
-    if (n_granules > kMaxGranules) {
-      return fail(report, kIoInvalid, "too many granules");
-    }
     *out = ParityCheck{};
     Bdev* first = p.bdev != nullptr ? p.bdev : q.bdev;
     const int device = select_device(all, first);
@@ -531,6 +626,93 @@ int bdev_parity_rebuild_sync(const std::vector<ParityMember>& data,
       if (wq.bdev != nullptr) touched.push_back(wq);
       return encode_validated(data, touched, wp, wq, length, report);
     }
+    return kIoOk;
+  } catch (const std::exception&) {
+    return fail(report, kIoFailed, "I/O failed");
+  }
+}
+
+int bdev_parity_update_sync(const std::vector<ParityMember>& data,
+                            ParityMember p, ParityMember q,
+                            const std::vector<ParityMember>& bases,
+                            uint64_t length, uint32_t granule,
+                            uint32_t max_report, bool refresh,
+                            DiffStats* changed, std::vector<uint64_t>* bitmap,
+                            ParityReport* report) {
+  try {
+    std::vector<ParityMember> all;
+    int status = validate_set(data, p, q, length, &all, report);
+    if (status != kIoOk) return status;
+    if (changed == nullptr || bitmap == nullptr) {
+      return fail(report, kIoInvalid, "no result to fill");
+    }
+    if (bases.size() != data.size()) {
+      return fail(report, kIoInvalid, "one base slot per data member is needed");
+    }
+    const uint64_t bs = all[0].bdev->block_size();
+    std::vector<ParityMember> tracked;
+    for (const ParityMember& b : bases) {
+      if (b.bdev == nullptr) continue;
+      if (b.bdev->block_size() != bs) {
+        return fail(report, kIoInvalid,
+                    "a base does not have the set's block size");
+      }
+      if (b.offset % bs != 0) {
+        return fail(report, kIoInvalid,
+                    "offsets must be multiples of the block size");
+      }
+      const uint64_t size = b.bdev->size_bytes();
+      if (length > size || b.offset > size - length) {
+        return fail(report, kIoInvalid, "base range out of bounds");
+      }
+      for (const ParityMember& m : all) {
+        if (same_store(b.bdev, m.bdev)) {
+          return fail(report, kIoInvalid,
+                      "a base shares a bdev or backing store with a member");
+        }
+      }
+      for (const ParityMember& other : tracked) {
+        if (same_store(b.bdev, other.bdev)) {
+          return fail(report, kIoInvalid,
+                      "two bases share a bdev or backing store");
+        }
+      }
+      tracked.push_back(b);
+    }
+    if (tracked.empty()) {
+      return fail(report, kIoInvalid, "no base given: nothing is tracked");
+    }
+    status = validate_granule(bs, length, granule, report);
+    if (status != kIoOk) return status;
+    if ((p.bdev != nullptr && p.bdev->claimed()) ||
+        (q.bdev != nullptr && q.bdev->claimed())) {
+      return fail(report, kIoFailed,
+                  "a parity bdev is claimed; update runs offline only");
+    }
+    if (refresh) {
+      for (const ParityMember& b : tracked) {
+        if (b.bdev->claimed()) {
+          return fail(report, kIoFailed,
+                      "a base bdev is claimed; refresh runs offline only");
+        }
+      }
+    }
+    const uint64_t n_granules = length / granule;
+    *changed = DiffStats{};
+    bitmap->clear();
+    std::vector<ParityMember> touched = all;
+    touched.insert(touched.end(), tracked.begin(), tracked.end());
+    Bdev* first = p.bdev != nullptr ? p.bdev : q.bdev;
+    const int device = select_device(touched, first);
+    if (report != nullptr) report->on_gpu = device >= 0;
+    status = device >= 0
+                 ? parity_update_gpu(device, device_set(data), device_set(bases),
+                                     device_ptr(p), device_ptr(q), n_granules,
+                                     granule, refresh, bitmap)
+                 : update_generic(data, p, q, bases, length, granule, refresh,
+                                  bitmap);
+    if (status != kIoOk) return fail(report, status, "I/O failed");
+    fill_stats(*bitmap, n_granules, max_report, changed);
     return kIoOk;
   } catch (const std::exception&) {
     return fail(report, kIoFailed, "I/O failed");

@@ -1,12 +1,15 @@
-// MI355X (gfx950) P+Q parity across HBM bdevs: encode, check and
-// rebuild (definitions in hipstore/parity.h). Like bulk_ops.hip, each
+// MI355X (gfx950) P+Q parity across HBM bdevs: encode, check, rebuild
+// and update (definitions in hipstore/parity.h). Like bulk_ops.hip, each
 // call owns its stream, runs to completion and returns.
 //
 // Data movement: HBM -> VGPR -> HBM, nothing is staged through LDS.
 // Every byte of every member is read exactly once, by one lane, and no
 // lane ever needs a byte another lane loaded, so LDS would only add a
 // round trip. (k_parity_check uses 32 bytes of LDS to join the four
-// waves' bitmap slices, never for data.)
+// waves' bitmap slices, never for data.) The same holds for
+// k_parity_update: a lane's 16 bytes of a member, of its base and of the
+// stored parity meet in that lane's registers; what the lanes of a slab
+// share is one bit per decision, and a ballot carries that.
 //
 // Work split: a lane owns one 16-byte column of the range at a time and
 // walks the k members of that column from k-1 down to 0 (Horner:
@@ -227,6 +230,161 @@ __global__ __launch_bounds__(kParityThreads) void k_parity_rebuild(
   }
 }
 
+// --- update ------------------------------------------------------------------
+//
+// One step of the update walk: member `idx` of one slab (64 lanes x one
+// 16-byte column). `nw` / `old` are the member's and its base's columns,
+// loaded by the caller ahead of this chain (zero in a lane past the
+// granule's end, so such a lane contributes nothing). An untracked
+// member keeps the doubling and nothing else. With kRefresh a member
+// that differs from its base anywhere in the slab stores its column into
+// the base's slab: one wave-uniform decision per member and slab.
+template <bool kP, bool kQ, bool kRefresh>
+__device__ __forceinline__ void update_fold(const ParitySet& bases,
+                                            uint32_t idx, uint64_t col,
+                                            bool active, const uint4 nw,
+                                            const uint4 old, uint4& p,
+                                            uint4& q, uint32_t& dirty) {
+  if (kQ) q = gf_double16(q);
+  const uint8_t* base = bases.data[idx];
+  if (base == nullptr) return;  // wave-uniform
+  const uint4 d = xor16(nw, old);
+  const uint32_t any = or_reduce16(d);
+  if (kP) p = xor16(p, d);
+  if (kQ) q = xor16(q, d);
+  dirty |= any;
+  if (kRefresh && __ballot(any != 0) != 0ull && active) {
+    reinterpret_cast<uint4*>(const_cast<uint8_t*>(base))[col] = nw;
+  }
+}
+
+// Member `idx`'s and its base's column: zero for an untracked member
+// (wave-uniform) and in a lane past the granule's end. A branch, not a
+// conditional expression between a load and a zero: that one selects
+// between two addresses and turns the loads into flat loads.
+__device__ __forceinline__ void update_load(const ParitySet& set,
+                                            const ParitySet& bases,
+                                            uint32_t idx, uint64_t col,
+                                            bool active, uint4& nw,
+                                            uint4& old) {
+  nw = make_uint4(0, 0, 0, 0);
+  old = make_uint4(0, 0, 0, 0);
+  const uint8_t* base = bases.data[idx];
+  if (base != nullptr && active) {
+    nw = reinterpret_cast<const uint4*>(set.data[idx])[col];
+    old = reinterpret_cast<const uint4*>(base)[col];
+  }
+}
+
+// The P and / or Q deltas of one slab over the tracked members below
+// `top` (the highest tracked index + 1: the doublings of a still-zero q
+// above it are never executed), Horner as parity_walk and with its
+// unroll: the loads of the tracked members among kParityUnroll indices,
+// two per member, are issued before any of their chains. Returns the
+// lane's OR of its d_i, which decides the slab's bit and whether parity
+// is touched: not p | q, which cancelling deltas leave zero.
+template <bool kP, bool kQ, bool kRefresh>
+__device__ __forceinline__ uint32_t update_walk(const ParitySet& set,
+                                                const ParitySet& bases,
+                                                uint32_t top, uint64_t col,
+                                                bool active, uint4& p,
+                                                uint4& q) {
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  p = zero;
+  q = zero;
+  uint32_t dirty = 0;
+  uint32_t i = top;
+  for (; i >= kParityUnroll; i -= kParityUnroll) {
+    uint4 nw[kParityUnroll];
+    uint4 old[kParityUnroll];
+#pragma unroll
+    for (uint32_t j = 0; j < kParityUnroll; ++j) {
+      update_load(set, bases, i - 1 - j, col, active, nw[j], old[j]);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kParityUnroll; ++j) {
+      update_fold<kP, kQ, kRefresh>(bases, i - 1 - j, col, active, nw[j],
+                                    old[j], p, q, dirty);
+    }
+  }
+  while (i > 0) {
+    --i;
+    uint4 nw, old;
+    update_load(set, bases, i, col, active, nw, old);
+    update_fold<kP, kQ, kRefresh>(bases, i, col, active, nw, old, p, q, dirty);
+  }
+  return dirty;
+}
+
+// Diff, parity read-modify-write and base refresh in one pass. Work
+// split of k_parity_check, because the output is a granule bitmap: a
+// workgroup per 64-granule word per grid-stride step, a wave per
+// 16-granule slice; inside a granule the wave takes one 1 KiB slab at a
+// time, and in a ragged last slab (a 512-byte granule is half a slab)
+// the lanes at or past n16 idle: they load nothing, store nothing and
+// vote 0, and the slab loop itself stays wave-uniform so every ballot
+// sees the whole wave.
+//
+// Per slab the wave decides by ballot: if no lane saw a difference the
+// stored parity of the slab is neither read nor written; otherwise every
+// active lane loads its P / Q column, XORs the delta in and stores it.
+// The granule's bit is the OR of its slabs' ballots, so a clear bit
+// means no parity byte of the granule was written. The write predicate
+// is per slab, not per lane, so that a dirty slab is rewritten as whole
+// 1 KiB runs and not as scattered 16-byte columns; a per-lane predicate
+// would store fewer bytes. Nobody has measured one against the other.
+//
+// The bases are distinct from the members and the parities (validated
+// on the host), so a refresh store never feeds a later load.
+template <bool kP, bool kQ, bool kRefresh>
+__global__ __launch_bounds__(kWavesPerWg * 64) void k_parity_update(
+    const ParitySet set, const ParitySet bases, uint32_t top, uint4* p_io,
+    uint4* q_io, uint64_t n_granules, uint32_t granule_bytes,
+    unsigned long long* __restrict__ bitmap) {
+  __shared__ uint32_t partial[kWavesPerWg];
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n16 = granule_bytes >> 4;
+  const uint64_t n_words = (n_granules + 63) >> 6;
+  for (uint64_t w = blockIdx.x; w < n_words; w += gridDim.x) {
+    const uint64_t g0 = w * 64 + wave * kCheckGranulesPerWave;
+    uint32_t bits = 0;
+    for (uint32_t j = 0; j < kCheckGranulesPerWave; ++j) {
+      const uint64_t g = g0 + j;
+      if (g >= n_granules) break;  // wave-uniform
+      const uint64_t col0 = g * n16;
+      for (uint32_t s = 0; s < n16; s += 64) {  // wave-uniform
+        const bool active = s + lane < n16;
+        const uint64_t col = col0 + s + lane;  // dereferenced if active
+        uint4 p, q;
+        const uint32_t dirty = update_walk<kP, kQ, kRefresh>(
+            set, bases, top, col, active, p, q);
+        if (__ballot(dirty != 0) == 0ull) continue;
+        bits |= 1u << j;
+        if (active) {
+          uint4 ps, qs;
+          if (kP) ps = p_io[col];
+          if (kQ) qs = q_io[col];
+          if (kP) p_io[col] = xor16(ps, p);
+          if (kQ) q_io[col] = xor16(qs, q);
+        }
+      }
+    }
+    if (lane == 0) partial[wave] = bits;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long word = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kWavesPerWg; ++k) {
+        word |= static_cast<unsigned long long>(partial[k])
+                << (k * kCheckGranulesPerWave);
+      }
+      bitmap[w] = word;
+    }
+    __syncthreads();  // partial[] is rewritten by the next step
+  }
+}
+
 // --- launch helpers ----------------------------------------------------------
 
 uint32_t column_grid(uint64_t n16) {
@@ -252,13 +410,19 @@ void with_parity_flags(bool want_p, bool want_q, Go go) {
   }
 }
 
-// Per-thread pinned bitmaps of the check: the kernel writes them in
-// place (zero-copy, 1/4096 of the data at 512-byte granules).
+// Per-thread pinned bitmaps of the check and (p_words only) the update:
+// the kernel writes them in place (zero-copy, 1/4096 of the data at
+// 512-byte granules).
 struct CheckCtx {
   PinnedBuf<unsigned long long> p_words;
   PinnedBuf<unsigned long long> q_words;
 };
 constexpr uint64_t kMinCheckWords = 4096;
+
+CheckCtx& check_ctx() {
+  thread_local CheckCtx ctx;
+  return ctx;
+}
 
 }  // namespace
 
@@ -314,7 +478,7 @@ int parity_check_gpu(int device, const ParitySet& set, const uint8_t* p,
   }
   const uint64_t n_words = (n_granules + 63) / 64;
   try {
-    thread_local CheckCtx ctx;
+    CheckCtx& ctx = check_ctx();
     const uint64_t room = std::max(n_words, kMinCheckWords);
     unsigned long long* pw = ctx.p_words.reserve(room);
     unsigned long long* qw = ctx.q_words.reserve(room);
@@ -363,6 +527,51 @@ int parity_rebuild_gpu(int device, const ParitySet& set, const uint8_t* p,
                          reinterpret_cast<uint4*>(out_b), n16);
     });
   });
+}
+
+int parity_update_gpu(int device, const ParitySet& set, const ParitySet& bases,
+                      uint8_t* p, uint8_t* q, uint64_t n_granules,
+                      uint32_t granule, bool refresh,
+                      std::vector<uint64_t>* words) {
+  if (set.k == 0 || set.k > kParityMaxData || bases.k != set.k ||
+      (p == nullptr && q == nullptr) || n_granules == 0 || granule == 0 ||
+      granule % 16 != 0 || words == nullptr) {
+    return kIoInvalid;
+  }
+  uint32_t top = 0;  // highest tracked index + 1
+  for (uint32_t i = 0; i < set.k; ++i) {
+    if (bases.data[i] == nullptr) continue;
+    if (set.data[i] == nullptr) return kIoInvalid;
+    top = i + 1;
+  }
+  if (top == 0) return kIoInvalid;
+  const uint64_t n_words = (n_granules + 63) / 64;
+  try {
+    unsigned long long* host_words =
+        check_ctx().p_words.reserve(std::max(n_words, kMinCheckWords));
+    unsigned long long* dev_words = device_view(host_words);
+    const int status = run_granule_kernel(device, [&](hipStream_t stream) {
+      with_parity_flags(p != nullptr, q != nullptr, [&](auto kp, auto kq) {
+        auto launch = [&](auto kr) {
+          hipLaunchKernelGGL(
+              (k_parity_update<kp.value, kq.value, kr.value>),
+              dim3(check_grid(n_granules)), dim3(kWavesPerWg * 64), 0, stream,
+              set, bases, top, reinterpret_cast<uint4*>(p),
+              reinterpret_cast<uint4*>(q), n_granules, granule, dev_words);
+        };
+        if (refresh) {
+          launch(std::true_type{});
+        } else {
+          launch(std::false_type{});
+        }
+      });
+    });
+    if (status != kIoOk) return status;
+    words->assign(host_words, host_words + n_words);
+    return kIoOk;
+  } catch (const std::exception&) {
+    return kIoFailed;
+  }
 }
 
 }  // namespace hipstore

@@ -1384,6 +1384,61 @@ PYBIND11_MODULE(_hipstore, m) {
      "Rewrite the one or two members named by `lost` (data indices, \"p\", "
      "\"q\") from the others; the bdevs in those slots are the targets");
 
+  m.def("parity_update", [](std::vector<BdevPtr> data, BdevPtr p, BdevPtr q,
+                            std::vector<BdevPtr> bases,
+                            std::vector<uint64_t> data_offsets,
+                            std::vector<uint64_t> base_offsets,
+                            uint64_t p_offset, uint64_t q_offset,
+                            uint64_t length, uint32_t granule,
+                            uint32_t max_report, bool refresh) {
+    if (!base_offsets.empty() && base_offsets.size() != bases.size()) {
+      throw std::invalid_argument("parity_update: one offset per base slot");
+    }
+    std::vector<ParityMember> base_members;
+    for (size_t i = 0; i < bases.size(); ++i) {
+      base_members.push_back(
+          {bases[i].get(),
+           bases[i] && !base_offsets.empty() ? base_offsets[i] : 0});
+    }
+    if (granule == 0 && !data.empty() && data[0]) {
+      granule = static_cast<uint32_t>(data[0]->block_size());
+    }
+    ParityArgs a = parity_args(data, p, q, data_offsets, p_offset, q_offset,
+                               length, granule);
+    if (length == 0) {  // the bases bound the default extent too
+      std::vector<ParityMember> bound = a.data;
+      bound.insert(bound.end(), base_members.begin(), base_members.end());
+      a.length = parity_common_length(bound, a.p, a.q, granule);
+    }
+    ParityReport report;
+    DiffStats changed;
+    std::vector<uint64_t> words;
+    int status;
+    {
+      py::gil_scoped_release release;
+      status = bdev_parity_update_sync(a.data, a.p, a.q, base_members,
+                                       a.length, granule, max_report, refresh,
+                                       &changed, &words, &report);
+    }
+    parity_raise("parity_update", status, report);
+    py::dict d;
+    d["length"] = a.length;
+    d["on_gpu"] = report.on_gpu;
+    d["granule"] = granule;
+    d["changed"] = parity_stats_dict(changed, words);
+    return d;
+  }, py::arg("data"), py::arg("p") = py::none(), py::arg("q") = py::none(),
+     py::arg("bases") = std::vector<BdevPtr>{},
+     py::arg("data_offsets") = std::vector<uint64_t>{},
+     py::arg("base_offsets") = std::vector<uint64_t>{},
+     py::arg("p_offset") = 0, py::arg("q_offset") = 0, py::arg("length") = 0,
+     py::arg("granule") = 0, py::arg("max_report") = 16,
+     py::arg("refresh") = false,
+     "Bring stored P / Q up to date from the tracked data bdevs and the "
+     "clones of their earlier state in `bases` (None = untracked, not "
+     "read); \"changed\" is shaped like a bdev_diff result. refresh=True "
+     "also stores the changed bytes into the bases");
+
   m.def("persistent_probe", &persistent_probe, py::arg("device") = 0,
         py::arg("flags") = 1,
         py::call_guard<py::gil_scoped_release>());

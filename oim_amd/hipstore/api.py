@@ -332,6 +332,35 @@ def bdev_parity_rebuild(client: Client, data: List[str],
     return client.invoke("bdev_parity_rebuild", params)
 
 
+def bdev_parity_update(client: Client, data: List[str],
+                       bases: List[Optional[str]],
+                       p: Optional[str] = None, q: Optional[str] = None,
+                       offset: int = 0, length: Optional[int] = None,
+                       granule: Optional[int] = None,
+                       max_report: Optional[int] = None,
+                       refresh: bool = False) -> Dict:
+    """Bring the stored parity in `p` / `q` up to date after data bdevs
+    changed, from clones of their earlier state: `bases` has one entry per
+    entry of `data`, a bdev holding that member as of the last time the
+    parity was right (a `bdev_clone`), or None for a member that did not
+    change (it is not read). Parity is rewritten only in granules where a
+    tracked member differs from its base. With `refresh` the changed
+    bytes are also stored into the bases, which are then ready for the
+    next cycle; without it a second call undoes the first. Offline only.
+
+    Returns {length, granule, on_gpu, changed: {granules, mismatched,
+    first_mismatches}}."""
+    params = _parity_params(data, p, q, offset, length)
+    params["bases"] = list(bases)
+    if granule is not None:
+        params["granule"] = granule
+    if max_report is not None:
+        params["max_report"] = max_report
+    if refresh:
+        params["refresh"] = True
+    return client.invoke("bdev_parity_update", params)
+
+
 def _map_params(params: Dict, map_algorithm: Optional[str],
                 map_key_file: Optional[str]) -> None:
     if map_algorithm is not None:
